@@ -14,7 +14,13 @@ Weak scaling: N GPUs compress an N x 10^8-byte stream; every rank holds its 10^8
 every rank plans its own slice (one all_gather of per-slice RLE1 totals, one of the boundary targets the slices hand on: no rank waits for another rank's plan), the encoded segments
 are gathered to rank 0 (compressjs_amd/dist.py).  Prints ONE JSON line (rank 0).
 
-What the line carries besides the driver's contract:
+A plain run sets up, warms up, times --steps steps and prints the line (value = MB/s over the timed steps, ms_per_step =
+wall-clock milliseconds of one timed step).  --dump-outputs DIR writes the .bz2 stream of the last timed step to DIR as .npy
+files (dump_outputs below) before the line is printed.  Everything else - the checks against the reference's digests, the
+oracle and two decoders, and the secondary measurements below - runs only with --full, after the timed region; a plain run
+leaves those fields null.
+
+What the line carries besides the driver's contract, with --full:
   config.bit_exact_vs_reference_digest   sha256 of the WHOLE stream == what the reference itself (node 12) produced
                                          on the same bytes (tests/golden/golden_big.json), all 112 blocks
   config.pcie_inclusive_mb_s             the same step through cjs_bz2_compress (host buffer in, host buffer out), mean of the same number of steps
@@ -60,6 +66,26 @@ import torch.distributed as dist  # noqa: E402
 KERNELS = [("k1f_bsort", 16.0), ("k1r_round", 20.0), ("k1d_build", 8.0), ("k1d_round", 20.0), ("k1d_med", None), ("k1d_large", None),
            ("k1d_update", 20.0), ("k1f_task", None)]
 E2E_ALG_BYTES = 16.0            # 14 + 4 rho + c bytes per input byte, nominal 16 for enwik8-shaped text
+DUMP_SAMPLE = 8 << 20           # --dump-outputs: at most this many bytes of the stream, as float32 (32 MB)
+DUMP_SEED = 0
+DUMP_PIECE = 1 << 16
+
+
+def dump_outputs(d: str, comp: bytes):
+    """--dump-outputs DIR: the compressed stream the last timed step returned, as arrays two builds can be compared by.
+      stream.npy        float32, the stream's bytes: all of them when there are at most DUMP_SAMPLE, else DUMP_SAMPLE of them
+                        at positions drawn without replacement with seed DUMP_SEED, in increasing order
+      stream_crc32.npy  float64, zlib.crc32 of every DUMP_PIECE-byte piece of the whole stream (covers what a sample leaves out)
+      stream_len.npy    float64, [bytes in the stream]"""
+    import zlib
+    os.makedirs(d, exist_ok=True)
+    a = np.frombuffer(comp, dtype=np.uint8)
+    if a.size > DUMP_SAMPLE:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))]
+    np.save(os.path.join(d, "stream.npy"), a.astype(np.float32))
+    np.save(os.path.join(d, "stream_crc32.npy"),
+            np.array([zlib.crc32(comp[o:o + DUMP_PIECE]) for o in range(0, len(comp), DUMP_PIECE)], dtype=np.float64))
+    np.save(os.path.join(d, "stream_len.npy"), np.array([len(comp)], dtype=np.float64))
 
 
 def reference_baseline(ctx, host: np.ndarray, level: int, nbytes: int):
@@ -120,16 +146,18 @@ def bench_bwtc(args):
     for _ in range(args.steps):
         out = ctx.bwtc_compress(host, args.level)
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     sha = hashlib.sha256(out).hexdigest()
     gold = {}
     gpath = os.path.join(ROOT, "tests", "golden", "golden_big.json")
-    if os.path.exists(gpath):
+    if args.full and os.path.exists(gpath):
         gold = json.load(open(gpath))["vectors"]
     g = gold.get("%s:%d:bwtc:%d" % (wl, args.size, args.level))
     vs_ref = None if g is None else bool(g["out_sha256"] == sha and g["out_len"] == len(out))
     # the same stream with the model on the host (round-1 path) must give the same bytes; and back through BWTC.decompressFile
     back = None
-    if not args.no_verify and args.size <= 30_000_000:
+    if args.full and not args.no_verify and args.size <= 30_000_000:
         back = bool(ctx.bwtc_decompress(np.frombuffer(out, dtype=np.uint8)) == host.tobytes())
     # the dominant GPU kernel of this path is k10_model (the adaptive FenwickModel: one wave per block, a serial recurrence): its
     # algorithmic bytes are 2 (symbol read) + 8 (triple written) per encodeFreq call - measured live with HIP events around the launch
@@ -177,7 +205,13 @@ def main():
     ap.add_argument("--codec", default="bz2", choices=["bz2", "bwtc"],
                     help="bwtc: BWTC.compressFile -9 (BASELINE.json configs[4]; N = 1, host buffers in and out: its range coder is serial "
                          "host code, lib/RangeCoder.js; BWT, MTF/RLE2 and the adaptive FenwickModel run on the GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the checks (reference digests, oracle, libbz2 and GPU decoders) and the "
+                         "secondary measurements (decoder, host-to-host, E8S-A and sample5 rates, roofline pass, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the stream of the last timed step to DIR as .npy files (float32 / float64, dump_outputs)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
     if args.codec == "bwtc":
         return bench_bwtc(args)
 
@@ -275,11 +309,15 @@ def main():
     if rank == 0:
         import ctypes as C
         comp = out.cpu().numpy().tobytes()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, comp)
         sha = hashlib.sha256(comp).hexdigest()
+        # everything from here to the line runs with --full only: a plain run's checks and legs stay off
+        verify = args.full and not args.no_verify
         # ---- parity of the WHOLE stream: the digest the reference itself produced on these bytes -------------
         gold = {}
         gpath = os.path.join(ROOT, "tests", "golden", "golden_big.json")
-        if os.path.exists(gpath):
+        if args.full and os.path.exists(gpath):
             gold = json.load(open(gpath))["vectors"]
         gkey = "%s:%d:bz2:%d" % (args.workload, total, args.level)
         g = gold.get(gkey)
@@ -287,7 +325,7 @@ def main():
         # N > 1 with a pinned digest (tests/golden/make_golden_jobs.py: reference-made at N = 2, 4 and 8 since round 6 - the line says which in reference_digest_made_by): the digest
         # IS the check; naming the whole N-document stream on rank 0's host again takes minutes and is only done without one
         digest_only = world > 1 and g is not None and not args.full_verify
-        if host is None and not digest_only:
+        if host is None and not digest_only and args.full:
             host = workloads.world_stream(args.workload, args.size, world)
         if g is not None:
             if host is not None:
@@ -295,7 +333,7 @@ def main():
             vs_ref = bool(sha == g["out_sha256"] and len(comp) == g["out_len"])
         verified, port, pcie, decode_mb_s = None, None, None, None
         prefix_ok = None
-        if digest_only and not args.no_verify:
+        if digest_only and verify:
             # N > 1 with a pinned digest: besides the digest, an independent decoder (libbz2) on a bounded prefix of the assembled stream
             # against what rank 0 itself holds - its own document, the first args.size bytes of the job
             import bz2
@@ -305,7 +343,7 @@ def main():
                 prefix_ok = bool(bz2.BZ2Decompressor().decompress(comp, limit) == mine)
             except Exception:                                # noqa: BLE001
                 prefix_ok = False
-        if not args.no_verify and not digest_only:
+        if verify and not digest_only:
             import bz2
             # independent decoder (libbz2), bounded to keep the default run short
             limit = min(total, 200_000_000)
@@ -346,7 +384,7 @@ def main():
         #      largest total on this workload is the line's dominant kernel -----------------------------------------------
         prof_steps, kms, dom = 3, {}, None
         avg_ms, launches, elements, alg_per_el = 0.0, 0, 0, None
-        if world == 1:
+        if world == 1 and args.full:
             prev_streams = os.environ.get("CJS_STREAMS")           # (restored below: the E8S-A and PCIe legs run under the caller's setting)
             os.environ["CJS_STREAMS"] = "1"
             ctx1 = Context(local, args.batch)
@@ -384,7 +422,7 @@ def main():
                 traffic_build = tj.get("build")
         # ---- SURVEY.md 8(d)'s real-text headline (E8S-A: test/sample5.ref || sample4.ref tiled) in the same line --------------
         e8 = {"mb_s": None, "ms": None, "exact": None}
-        if world == 1 and args.workload != "e8sa" and workloads.have_fixtures() and not args.no_verify:
+        if world == 1 and verify and args.workload != "e8sa" and workloads.have_fixtures():
             h2 = workloads.stream("e8sa", args.size)
             d2 = torch.from_numpy(h2).to(dev)
             for _ in range(args.warmup):                       # (the headline's own warm-up and step counts)
@@ -403,9 +441,8 @@ def main():
         # ---- BASELINE.json configs[1]: test/sample5.ref (2 130 640 bytes, three blocks), bzip2 -9, ONE call through cjs_bz2_compress
         #      (host buffer in, host buffer out): the small-input rate, bound by the latency of the kernel chain, not by throughput
         s5 = {"mb_s": None, "ms": None, "exact": None}
-        s5path = os.path.join(ROOT, "oracle", "_ref", "fixtures", "sample5.ref")
-        if world == 1 and os.path.exists(s5path) and not args.no_verify:
-            h5 = np.fromfile(s5path, dtype=np.uint8)
+        h5 = workloads.refdata.read("sample5.ref") if world == 1 and verify else None
+        if h5 is not None:
             b5 = np.zeros(int(ctx.L.cjs_bz2_compress_bound(h5.size)), dtype=np.uint8)
             n5 = 0
             for _ in range(3):
@@ -419,7 +456,7 @@ def main():
                   "exact": bool(args.level == 9 and n5 == 274768 and hashlib.sha256(b5[:n5].tobytes()).hexdigest().startswith("236be53b"))}
         wall = elapsed / args.steps
         ref_line = None
-        if world == 1 and not args.no_verify:
+        if world == 1 and verify:
             ref_line = reference_baseline(ctx, host, args.level, min(args.ref_sample, total))
         whole = None
         if g is not None and "mb_per_s" in g and world == 1:

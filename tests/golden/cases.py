@@ -1,18 +1,16 @@
 """Catalogue of parity inputs.  Every input is either synthesised deterministically
 (compressjs_amd.synth) or one of the reference's own test fixtures (test/sample*.ref), which
-are looked up under /root/reference/test (build container) or oracle/_ref/fixtures (staged
-there by __graft_entry__.build(); git-ignored, travels with gpurun).  Fixtures are never
-committed."""
+are stored under tests/golden/fixtures (refdata.py)."""
 from __future__ import annotations
 
 import os
 import numpy as np
 
+import refdata
 from compressjs_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-FIXTURE_DIRS = ["/root/reference/test", os.path.join(ROOT, "oracle", "_ref", "fixtures")]
 
 
 def _lcg_plus(n, seed, tail):
@@ -76,24 +74,13 @@ BWT_CASES = ["sample0", "sample1", "sample3", "a1", "a4", "ab500", "abc_tie", "b
              "bytes40", "text1k", "text100k", "periodic_ab_100k", "lcg99981", "runs300k"]
 
 
-def fixture_path(name: str):
-    for d in FIXTURE_DIRS:
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return p
-    return None
-
-
 def case_input(cid: str):
     """Return the input bytes (np.uint8 array) for a case id, or None if it is a reference
-    fixture that is not available on this machine."""
+    fixture that is not stored."""
     b = CASES[cid][0]
     kind = b[0]
     if kind == "fixture":
-        p = fixture_path(b[1])
-        if p is None:
-            return None
-        return np.fromfile(p, dtype=np.uint8)
+        return refdata.read(b[1])
     if kind == "bytes":
         return np.frombuffer(b[1], dtype=np.uint8).copy()
     if kind == "all_bytes":

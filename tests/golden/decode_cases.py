@@ -3,17 +3,17 @@
 Every stream is rebuilt deterministically at test time from a recipe:
   * `enc`  : the oracle's encoder (bit-identical to the reference's, pinned by golden.json),
   * `lib`  : libbzip2 through Python's bz2 module (a different encoder: other tables, 6 groups),
-  * `fix`  : test/sample*.bz2 of the reference (libbzip2-made; staged under oracle/_ref/fixtures),
+  * `fix`  : test/sample*.bz2 of the reference (libbzip2-made; stored under tests/golden/fixtures),
 then concatenated / truncated / corrupted.  golden_decode.json (make_golden_decode.py) records the
 sha256 of each stream and what the REFERENCE's Bzip2.decompressFile did with it.
 """
 import bz2
-import os
 
 import numpy as np
 
 import cases
 import oracle
+import refdata
 
 
 def _enc(cid, level):
@@ -25,11 +25,7 @@ def _lib(cid, level):
 
 
 def _fix(name):
-    for d in cases.FIXTURE_DIRS:
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return open(p, "rb").read()
-    return None
+    return refdata.read_bytes(name)
 
 
 def _flip(s, bit):

@@ -3,12 +3,12 @@
 cd ${GRAFT_REPO_ROOT:-.}
 R=$(pwd); O=$R/gpurun_out/r04; mkdir -p $O; export TMPDIR=/tmp
 # 1. the bench line (default workload; carries E8S-A in config.e8sa_*) and the secondary workloads of SURVEY.md 8(d)
-timeout 600 python bench.py 2>/dev/null | tail -1 > $O/r04_bench.json; cut -c1-300 $O/r04_bench.json; echo
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $O/r04_bench.json; cut -c1-300 $O/r04_bench.json; echo
 for w in e8sa lcg e8sb text; do
-  timeout 600 python bench.py --workload $w 2>/dev/null | tail -1 > $O/r04_bench_$w.json
+  timeout 600 python bench.py --full --workload $w 2>/dev/null | tail -1 > $O/r04_bench_$w.json
   python -c "import json; j=json.load(open('$O/r04_bench_$w.json')); print('$w', j['value'], 'MB/s', j['ms_per_step'], 'ms', 'bit_exact_vs_reference', j['config']['bit_exact_vs_reference_digest'], 'pcie', j['config']['pcie_inclusive_mb_s'], 'dominant', j['roofline']['kernel'], j['roofline']['frac'])"
 done
-timeout 600 python bench.py --codec bwtc 2>/dev/null | tail -1 > $O/r04_bench_bwtc.json; cut -c1-200 $O/r04_bench_bwtc.json; echo
+timeout 600 python bench.py --full --codec bwtc 2>/dev/null | tail -1 > $O/r04_bench_bwtc.json; cut -c1-200 $O/r04_bench_bwtc.json; echo
 # 2. per-kernel times, one stream (every kernel has the GPU to itself), rocprofv3 --kernel-trace --stats
 for w in enwik e8sa; do
   cd /tmp && CJS_STREAMS=1 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o r04_e2e_$w -- python $R/tests/gpu_r2_probe.py run $w --reps 5 > $O/e2e_$w.log 2>&1

@@ -32,12 +32,12 @@ def ctx():
 
 def test_every_golden_stream_digest(golden):
     """Bit-identical .bz2 output to the reference (node 12) on EVERY pinned input, incl. test/sample0..5.ref at
-    -1 and -9.  The reference's fixtures travel to the GPU box under oracle/_ref/fixtures
-    (__graft_entry__.build() stages them); without them this test fails, it does not skip."""
+    -1 and -9.  The reference's fixtures are stored under tests/golden/fixtures; without them
+    this test fails, it does not skip."""
     keys = sorted(k for k in golden if k.split(":")[1:2] == ["bz2"])
     assert len(keys) == sum(len(lv) for _, lv in cases.CASES.values()), "golden.json out of date: rerun tests/golden/make_golden.py"
     missing = sorted({k.split(":")[0] for k in keys if cases.case_input(k.split(":")[0]) is None})
-    assert not missing, "reference fixtures not staged for %s (run __graft_entry__.build() in the build container)" % missing
+    assert not missing, "reference fixtures missing from tests/golden/fixtures: %s" % missing
     n = 0
     for k in keys:
         cid, _, lv = k.split(":")
@@ -51,7 +51,7 @@ def test_every_golden_stream_digest(golden):
 def test_sample5_level9_headline_digest(golden):
     d = cases.case_input("sample5")
     if d is None:
-        pytest.skip("test/sample5.ref not staged (run __graft_entry__.build() in the build container)")
+        pytest.skip("test/sample5.ref missing from tests/golden/fixtures")
     o = Bzip2.compressFile(d, None, 9)
     assert len(o) == 274768 and _sha(o).startswith("236be53bab8972f04032ef88")
 
@@ -109,7 +109,7 @@ def test_full_size_workloads_vs_reference_digest(ctx, golden_big, name):
     """The other 10^8-byte streams of SURVEY.md 8(d) - E8S-A (test/sample5.ref || sample4.ref tiled), cfg4's random
     ASCII per GPU, E8S-B - against the digest of the reference's own output, and the leading blocks against the oracle."""
     if name in ("e8sa", "e8sb"):
-        assert workloads.have_fixtures(), "reference fixtures not staged (run __graft_entry__.build() in the build container)"
+        assert workloads.have_fixtures(), "reference fixtures missing from tests/golden/fixtures"
     d = workloads.stream(name, 100_000_000)
     g = golden_big["%s:100000000:bz2:9" % name]
     assert hashlib.sha256(d.tobytes()).hexdigest() == g["in_sha256"]
@@ -779,7 +779,7 @@ def test_two_ranks_sharing_the_gpu_real_library():
 def test_bwtc_level9_full_size_vs_reference_digest(ctx, golden_big):
     """BASELINE.json configs[4]: BWTC -9 on the 10^8-byte E8S-A stream - BWT.bwtransform (K1 linear), MTF/RLE2 (K2) and the
     adaptive FenwickModel (K10) on the GPU, range coder on the host - against the digest of the reference's own output."""
-    assert workloads.have_fixtures(), "reference fixtures not staged (run __graft_entry__.build() in the build container)"
+    assert workloads.have_fixtures(), "reference fixtures missing from tests/golden/fixtures"
     d = workloads.stream("e8sa", 100_000_000)
     g = golden_big["e8sa:100000000:bwtc:9"]
     a = ctx.bwtc_compress(d, 9)

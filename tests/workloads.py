@@ -8,9 +8,8 @@ the staged reference fixtures), hence under tests/ and not in the product packag
   e8sa   test/sample5.ref || test/sample4.ref tiled to n bytes (E8S-A, SURVEY.md 8d "headline")
   e8sb   order-2 Markov chain trained on the same 3 MB (E8S-B, "control")
 
-e8sa/e8sb need the reference's test fixtures (staged under oracle/_ref/fixtures by
-__graft_entry__.build(); never committed).  Nothing here reads /root/reference at run time
-on the GPU box: the fixtures travel with the snapshot."""
+e8sa/e8sb are built from the reference's test fixtures, stored under tests/golden/fixtures
+(tests/golden/refdata.py)."""
 from __future__ import annotations
 
 import os
@@ -20,8 +19,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import refdata  # noqa: E402
 from compressjs_amd import synth  # noqa: E402
-FIXTURE_DIRS = [os.path.join(ROOT, "oracle", "_ref", "fixtures"), "/root/reference/test"]
 NAMES = ("enwik", "text", "lcg", "e8sa", "e8sb")
 
 DESCRIPTIONS = {
@@ -34,24 +34,15 @@ DESCRIPTIONS = {
 }
 
 
-def fixture(name: str):
-    for d in FIXTURE_DIRS:
-        p = os.path.join(d, name)
-        if os.path.exists(p):
-            return p
-    return None
-
-
 def have_fixtures() -> bool:
-    return bool(fixture("sample5.ref") and fixture("sample4.ref"))
+    return refdata.read_bytes("sample5.ref") is not None and refdata.read_bytes("sample4.ref") is not None
 
 
 def _e8_base() -> np.ndarray:
-    parts = [fixture("sample5.ref"), fixture("sample4.ref")]
-    if not all(parts):
-        raise FileNotFoundError("e8sa/e8sb need test/sample5.ref and test/sample4.ref "
-                                "(staged by __graft_entry__.build())")
-    return np.concatenate([np.fromfile(p, dtype=np.uint8) for p in parts])
+    parts = [refdata.read("sample5.ref"), refdata.read("sample4.ref")]
+    if any(p is None for p in parts):
+        raise FileNotFoundError("e8sa/e8sb need test/sample5.ref and test/sample4.ref (tests/golden/fixtures)")
+    return np.concatenate(parts)
 
 
 def e8s_a(n: int) -> np.ndarray:
