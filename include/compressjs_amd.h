@@ -64,8 +64,8 @@ int64_t cjs_bz2_plan_block_start(cjs_ctx* ctx, uint32_t k);
  *   cjs_bz2_plan_scan   K0's scans over d_in; returns the input's own cost total;
  *   cjs_bz2_plan_cost   the input's own cost prefix at byte pos (pos = own_len: the slice's total);
  *   cjs_bz2_plan_phase  plans the blocks that START in [0, own_len), boundaries where the own prefix reaches phase + m * cap
- *                       (phase = (-(G(lo) + head-run correction)) mod cap; last != 0: d_in ends where the stream ends, the final
- *                       block may be short or absent, lib/Bzip2.js:916,922).  Returns their number - they are blocks 0 .. n-1
+ *                       (phase = (-(G(lo) + head-run correction)) mod cap; last != 0: no slice follows - d_in ends where the
+ *                       stream ends, the final block may be short or absent, lib/Bzip2.js:916,922).  Returns their number - they are blocks 0 .. n-1
  *                       for cjs_bz2_encode_blocks - or CJS_E_SPEC when the slice cannot be planned on its own (a boundary in a
  *                       long run, a block longer than the margin): the caller falls back to cjs_bz2_plan on more of the stream.
  *   cjs_bz2_plan_chain  (round 6) the same plan as a link of a chain: t0 = the value the own prefix reaches at the slice's FIRST
@@ -74,8 +74,12 @@ int64_t cjs_bz2_plan_block_start(cjs_ctx* ctx, uint32_t k);
  *                       run in the new block (lib/Bzip2.js:636-667) and moves every later boundary by a few bytes: the slice goes
  *                       on serially from there instead of refusing, and *t_next = the target of the first boundary at or beyond
  *                       own_len carries the shift to the slices behind it (the next slice's t0 = *t_next + G(lo) - G(lo') under
- *                       its own origin, not below 0).  CJS_E_SPEC only for a block longer than the margin or a run that fills a
- *                       block. */
+ *                       its own origin, not below 0).  CJS_E_SPEC is left for what a slice cannot plan on its own (k0_phase_chain):
+ *                       a block that starts in the slice and whose end the margin does not reach while last == 0; a run that
+ *                       fills a whole block; a block start that cuts a run which reaches the end of d_in while last == 0 (where
+ *                       the run ends is not known); more blocks than the plan has slots for (in_len / (cap / 2 + 1) + 2).
+ *                       cjs_bz2_plan_phase returns it too when a boundary moved and last == 0 (it has no *t_next to carry
+ *                       that). */
 #define CJS_E_SPEC (-25)
 int64_t cjs_bz2_plan_scan(cjs_ctx* ctx, const void* d_in, uint64_t in_len, int level);
 int64_t cjs_bz2_plan_cost(cjs_ctx* ctx, uint64_t pos);

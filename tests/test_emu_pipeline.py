@@ -766,8 +766,18 @@ def test_segmented_host_pipeline():
     assert r.returncode == 0, r.stdout + r.stderr
 
 
-def _segmented_check():
-    L = _lib.load(stagelib.build_emu())
+def _planted_runs():
+    """520 000 bytes of text with runs planted on and across the cuts of 120 000-byte segments."""
+    runs = synth.text_like(520_000, 8).copy()          # five segments on three contexts (two waves), runs on / across the cuts,
+    runs[119_990:120_004] = 65                          # a block boundary (99 981) right where a straddling run starts: refuse or agree
+    runs[239_998:240_001] = 66
+    runs[359_000:361_500] = 67
+    return runs
+
+
+def _segmented_check(lib_path=None):
+    """lib_path: the library to check (default: the CPU logic-debug build; tests/test_gpu_parity.py passes the product's)."""
+    L = _lib.load(lib_path or stagelib.build_emu())
     h = L.cjs_create(0, 4)
     try:
         for d, lv in ((synth.text_like(330_000, 21), 1), (synth.runs_mixed(300_000, 6), 1), (synth.text_like(185_000, 2), 1)):
@@ -776,10 +786,7 @@ def _segmented_check():
         # placement, seam bytes, trailer); zeros / runs take the replicated plan (every context plans the whole input, encodes its share)
         hs = [L.cjs_create(0, 4) for _ in range(3)]
         arr = (C.c_void_p * 3)(*hs)
-        runs = synth.text_like(520_000, 8).copy()          # five segments on three contexts (two waves), runs on / across the cuts,
-        runs[119_990:120_004] = 65                          # a block boundary (99 981) right where a straddling run starts: refuse or agree
-        runs[239_998:240_001] = 66
-        runs[359_000:361_500] = 67
+        runs = _planted_runs()
         took = []
         L.cjs_dbg_multi_fallbacks.restype = C.c_int
         for d, lv in ((np.zeros(260_000, np.uint8), 1), (synth.enwik_like(330_000, 4), 1), (synth.text_like(520_000, 7), 1), (runs, 1),
@@ -801,7 +808,10 @@ def _segmented_check():
         _lib._lib = L
         try:
             pc = Context(0, 2)
-            nser = pc.plan(torch.from_numpy(carried), 1)
+            d_in = torch.from_numpy(carried)
+            if lib_path:
+                d_in = d_in.cuda()                          # cjs_bz2_plan takes a DEVICE pointer: host memory serves only the CPU build
+            nser = pc.plan(d_in, 1)
             bnd = [pc.plan_block_start(k) for k in range(nser)]
             pc.close()
         finally:

@@ -701,6 +701,49 @@ def test_overlapped_host_path_same_bytes(ctx):
     assert _sha(ctx.compress(a[:12_000_000], 3)) == outs[0][2]
 
 
+def test_host_paths_at_their_smallest_vs_oracle():
+    """tests/test_emu_pipeline.py::_segmented_check - the CPU build's check of the host paths - on the product library: with
+    CJS_SEG_BYTES=120000 a segment is ~1.2 level-1 blocks, so 185 000 .. 520 000 bytes on contexts of 4 blocks put the "drop the last
+    block and restart there" seam, the segment-doubling branch, the incremental download, three-context windows, the replicated plan
+    and the carried-boundary replans on the hardware, every stream against the oracle's."""
+    import subprocess
+    import sys
+    code = ("import sys, os; sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, 'tests'));"
+            "sys.path.insert(0, os.path.join(%r, 'tests', 'golden'));"
+            "import test_emu_pipeline as t; t._segmented_check(%r)" % (ROOT, ROOT, ROOT, _lib.LIB_PATH))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CJS_SEG_BYTES="120000"), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+
+
+def test_overlapped_host_path_at_its_smallest_vs_oracle():
+    """compress_overlapped with slices of 2 level-1 blocks on a context of 4: 520 000 bytes cut into 3 slices (199 962, 199 962 and
+    the rest).  Both streams must be the oracle's; for the text the [ov] trace must report the slices, so that a detour through the
+    one-piece path does not pass; the stream with planted runs may fall back, only its bytes are checked."""
+    import re
+    import subprocess
+    import sys
+    code = (
+        "import sys, os; sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, 'tests'));"
+        "sys.path.insert(0, os.path.join(%r, 'tests', 'golden'))\n"
+        "import oracle, test_emu_pipeline as t\n"
+        "from compressjs_amd import synth\n"
+        "from compressjs_amd.bzip2 import Context\n"
+        "c = Context(0, 4)\n"
+        "text, runs = synth.text_like(520_000, 7), t._planted_runs()\n"
+        "assert c.compress(text, 1) == oracle.bz2_compress(text, 1), 'text'\n"
+        "sys.stderr.write('\\n--runs--\\n'); sys.stderr.flush()\n"
+        "assert c.compress(runs, 1) == oracle.bz2_compress(runs, 1), 'runs'\n"
+        "c.close()\n"
+    ) % (ROOT, ROOT, ROOT)
+    env = dict(os.environ, CJS_SLICE_BLOCKS="2", CJS_OV_TRACE="1")
+    env.pop("CJS_SEG_BYTES", None)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    m = re.search(r"\[ov\] (\d+) slices", r.stderr.split("--runs--")[0])
+    assert m and int(m.group(1)) >= 2, r.stderr[-3000:]
+
+
 def test_multi_context_fan_out_same_bytes():
     """cjs_bz2_compress_multi (what the Node addon calls with several devices configured): three contexts - here on the
     same GPU - take the segments round-robin; windows, parallel planning (or the replicated plan), bit-shifted placement, seam bytes, trailer."""
