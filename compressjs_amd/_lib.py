@@ -13,7 +13,7 @@ _lib = None
 
 # every symbol include/compressjs_amd.h declares (tests check the .so exports all of them)
 SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_device", "cjs_bz2_compress_bound", "cjs_bz2_compress",
-           "cjs_bz2_compress_device", "cjs_bz2_compress_multi", "cjs_bz2_plan", "cjs_bz2_plan_block_start", "cjs_bwtc_last_times", "cjs_bz2_plan_scan", "cjs_bz2_plan_cost", "cjs_bz2_plan_phase", "cjs_bz2_plan_chain", "cjs_bz2_encode_blocks", "cjs_bwtc_compress",
+           "cjs_bz2_compress_device", "cjs_bz2_compress_batch_bound", "cjs_bz2_compress_batch", "cjs_bz2_compress_batch_device", "cjs_bz2_compress_multi", "cjs_bz2_plan", "cjs_bz2_plan_block_start", "cjs_bwtc_last_times", "cjs_bz2_plan_scan", "cjs_bz2_plan_cost", "cjs_bz2_plan_phase", "cjs_bz2_plan_chain", "cjs_bz2_encode_blocks", "cjs_bwtc_compress",
            "cjs_bwtc_compress_bound",
            "cjs_last_device_ms", "cjs_last_block_count", "cjs_stream", "cjs_profile_enable",
            "cjs_profile_read", "cjs_profile_read_class", "cjs_bwt_cyclic", "cjs_bwt_cyclic_batch", "cjs_bwt_linear",
@@ -61,6 +61,14 @@ def load(path: str | None = None):
     L.cjs_bz2_compress.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64]
     L.cjs_bz2_compress_device.restype = C.c_int64
     L.cjs_bz2_compress_device.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64]
+    if hasattr(L, "cjs_bz2_compress_batch"):     # (absent from a library built before the batched entry existed - loaded for A/B timing through
+        #                                           COMPRESSJS_AMD_LIB; calling a missing entry raises AttributeError, build() checks SYMBOLS)
+        L.cjs_bz2_compress_batch_bound.restype = C.c_int64
+        L.cjs_bz2_compress_batch_bound.argtypes = [C.c_uint64, C.c_uint32]
+        L.cjs_bz2_compress_batch.restype = C.c_int64
+        L.cjs_bz2_compress_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp]
+        L.cjs_bz2_compress_batch_device.restype = C.c_int64
+        L.cjs_bz2_compress_batch_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp]
     L.cjs_bwtc_compress_bound.restype = C.c_int64
     L.cjs_bwtc_compress_bound.argtypes = [C.c_uint64]
     L.cjs_bwtc_compress.restype = C.c_int64

@@ -58,6 +58,45 @@ class Context:
         _lib.check(n, "cjs_bz2_compress")
         return out[:n].tobytes()
 
+    def compress_many(self, docs, level: int = 9) -> list:
+        """Many independent inputs in one call (cjs_bz2_compress_batch): one .bz2 stream per document, each equal to
+        compress(doc, level)."""
+        arrs = [np.ascontiguousarray(d, dtype=np.uint8).reshape(-1) for d in docs]
+        if not arrs:
+            level = int(level)
+            if level < 1 or level > 9:
+                _lib.check(-20, "cjs_bz2_compress_batch")
+            return []
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        cap = int(self.L.cjs_bz2_compress_batch_bound(int(off[-1]), len(arrs)))
+        out = self._staging(cap)
+        out_off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        n = self.L.cjs_bz2_compress_batch(self.h, flat.ctypes.data, off.ctypes.data, len(arrs), int(level), out.ctypes.data, cap,
+                                          out_off.ctypes.data)
+        _lib.check(n, "cjs_bz2_compress_batch")
+        return [out[int(out_off[k]):int(out_off[k + 1])].tobytes() for k in range(len(arrs))]
+
+    def compress_many_device(self, d_in, d_off, d_out, d_out_off, level: int = 9) -> int:
+        """The same with everything resident in HBM: d_in / d_out torch uint8 CUDA tensors, d_off / d_out_off 64-bit integer
+        CUDA tensors of count + 1 elements (document d = d_in[d_off[d]:d_off[d+1]]; stream d = d_out[d_out_off[d]:d_out_off[d+1]]).
+        Returns the total number of bytes written."""
+        import torch
+        count = int(d_off.numel()) - 1
+        for name, t, dt in (("d_in", d_in, (torch.uint8,)), ("d_out", d_out, (torch.uint8,)),
+                            ("d_off", d_off, (torch.int64, getattr(torch, "uint64", torch.int64))),
+                            ("d_out_off", d_out_off, (torch.int64, getattr(torch, "uint64", torch.int64)))):
+            if t.dtype not in dt or not t.is_contiguous():
+                raise ValueError("%s: a contiguous tensor of dtype %s" % (name, dt[0]))
+            if t.device != d_in.device:
+                raise ValueError("%s: on another device than d_in" % name)
+        if count < 0 or d_out_off.numel() < count + 1:
+            raise ValueError("d_off / d_out_off: count + 1 elements")
+        n = self.L.cjs_bz2_compress_batch_device(self.h, d_in.data_ptr(), d_off.data_ptr(), count, int(level),
+                                                 d_out.data_ptr(), d_out.numel(), d_out_off.data_ptr())
+        return _lib.check(n, "cjs_bz2_compress_batch_device")
+
     def bwtc_compress(self, data: np.ndarray, level: int = 9, declared_size=None) -> bytes:
         d = np.ascontiguousarray(data, dtype=np.uint8)
         cap = int(self.L.cjs_bwtc_compress_bound(d.size))
@@ -272,6 +311,17 @@ class Bzip2:
             raise ValueError("Invalid block size multiplier")                  # :888-890
         data = _coerce_input(inStream)
         return _deliver(default_context().compress(data, int(level)), outStream)
+
+    @staticmethod
+    def compressFiles(inputs, props=None):
+        """Many independent inputs, one .bz2 stream each, in one trip through the GPU (the reference has no batched entry):
+        [Bzip2.compressFile(x, None, props) for x in inputs], bit for bit."""
+        level = 9
+        if isinstance(props, (int, float)) and not isinstance(props, bool):   # lib/Bzip2.js:884-887
+            level = props
+        if level < 1 or level > 9 or level != int(level):
+            raise ValueError("Invalid block size multiplier")                  # :888-890
+        return default_context().compress_many([_coerce_input(x) for x in inputs], int(level))
 
     @staticmethod
     def decompressFile(inStream, outStream=None, multistream=False):

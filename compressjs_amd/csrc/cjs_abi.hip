@@ -145,7 +145,7 @@ int cjs::run_sub_batch(cjs_ctx* c, const K0Buf& K, const BatchGeom& g, u32 cap, 
     return pipe_run_block_stages(P, cap, st, 4);
 }
 
-int cjs::issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count, void* d_out, uint64_t out_cap) {
+int cjs::issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count, void* d_out, uint64_t out_cap, const K5Docs* docs) {
     BatchGeom g = make_geom(c->sub_blocks, cap);
     if (c->prof.enabled) c->prof_g = g;                   // (once, before the workers start: they only read it)
     // The blocks go out in batches of batch_blocks; a batch is cut into one sub-batch per stream by the streams' shares
@@ -183,7 +183,7 @@ int cjs::issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count,
             Pipe P;
             int rc = err.load() ? err.load() : run_sub_batch(c, K, g, cap, f, nb, si, d_out, out_cap, P, first + count);
             while (recorded.load(std::memory_order_acquire) != j) std::this_thread::yield();
-            if (!rc && !err.load()) rc = k5_run(P, cap, c->sub[si], j ? c->evScan[(j - 1) % ns] : nullptr, c->evScan[si], c->side ? c->evCrc[si] : nullptr);
+            if (!rc && !err.load()) rc = k5_run(P, cap, c->sub[si], j ? c->evScan[(j - 1) % ns] : nullptr, c->evScan[si], c->side ? c->evCrc[si] : nullptr, docs, f);
             if (rc) { int z = 0; err.compare_exchange_strong(z, rc); }
             recorded.store(j + 1, std::memory_order_release);
         }

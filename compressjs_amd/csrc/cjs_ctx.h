@@ -163,7 +163,7 @@ static inline Pipe stream_pipe(const cjs_ctx* c, void* d_out, uint64_t out_cap) 
 static inline void invalidate_plan(cjs_ctx* c) { c->plan_level = 0; c->plan_blocks = 0; c->scan_level = 0; }
 
 int grow(void** p, size_t* have, size_t need);
-int issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count, void* d_out, uint64_t out_cap);
+int issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count, void* d_out, uint64_t out_cap, const K5Docs* docs = nullptr);   // docs: a batch of documents (cjs_batch.hip)
 int run_sub_batch(cjs_ctx* c, const K0Buf& K, const BatchGeom& g, u32 cap, u32 f, u32 nb, u32 si, void* d_out, uint64_t out_cap,
                   Pipe& P, u32 total_blocks);
 // The stream cursor behind everything issued on `st`, waited for: the bits written so far, CJS_E_NOSPACE when the stream did not

@@ -403,14 +403,17 @@ int k5_stream_end(Pipe P, hipStream_t stream) {
 
 // `after` (optional): event of the previous batch's k5_blockscan -- bit offsets chain across
 // batches; `done` (optional) is recorded right after this batch's k5_blockscan.
-int k5_run(Pipe P, u32 max_n, hipStream_t stream, hipEvent_t after, hipEvent_t done, hipEvent_t crc_ready) {
+int k5_run(Pipe P, u32 max_n, hipStream_t stream, hipEvent_t after, hipEvent_t done, hipEvent_t crc_ready, const K5Docs* docs, u32 first_block) {
     const BatchGeom g = P.g;
     const u32 tiles = (max_n + 1 + K5_TILE - 1) / K5_TILE;
     if (crc_ready) HIP_CHECK_RET(hipStreamWaitEvent(stream, crc_ready, 0));
     hipLaunchKernelGGL(k5_header, dim3(g.nb), dim3(256), 0, stream, P);
     hipLaunchKernelGGL(k5_tilescan, dim3(g.nb), dim3(256), 0, stream, P);
     if (after) HIP_CHECK_RET(hipStreamWaitEvent(stream, after, 0));
-    hipLaunchKernelGGL(k5_blockscan, dim3(1), dim3(64), 0, stream, P);
+    if (docs) {
+        const int rc = k5_docscan_run(P, *docs, first_block, stream);
+        if (rc) return rc;
+    } else hipLaunchKernelGGL(k5_blockscan, dim3(1), dim3(64), 0, stream, P);
     if (done) HIP_CHECK_RET(hipEventRecord(done, stream));
     hipLaunchKernelGGL(k5_pack, dim3(tiles, g.nb), dim3(256), 0, stream, P);
     HIP_CHECK_RET(hipGetLastError());

@@ -105,7 +105,31 @@ int k2_run(Pipe P, u32 max_n, hipStream_t stream);
 int k10_model_run(Pipe P, u32* sylt, u32* tot, u32* ntri, u32 ostride, u32 ocap, hipStream_t stream);
 int k34_run(Pipe P, hipStream_t stream);
 int k3_alloc_lengths_run(long long* d_arr, const u32* d_off, u32 count, int maxlen, hipStream_t stream);
-int k5_run(Pipe P, u32 max_n, hipStream_t stream, hipEvent_t after = nullptr, hipEvent_t done = nullptr, hipEvent_t crc_ready = nullptr);   // crc_ready: the block CRCs were computed on another stream (k0_batch)
+// Batched compression (cjs_bz2_compress_batch*): document d of the batch is input bytes [off[d], off[d+1]) and becomes a .bz2 stream of
+// its own.  K0Docs (k0_docs.hip) is the plan's view of the documents, K5Docs (k5_docs.hip) the stream cursor's.
+struct K0Docs {
+    const u64* off;    // [count+1] document offsets (device), nondecreasing
+    u32 count;
+    u32* docFirst;     // [count+1] first block of document d (an empty document has none); [count] = blocks of the batch
+    u32* blkDoc;       // [maxBlocks] document of block k
+    u32* bad;          // [1] set when the plan needs more blocks than it has slots for
+};
+struct K5Docs {
+    const u32* docFirst;
+    const u32* blkDoc;
+    u64* outOff;       // [count+1] byte offset of stream d in the output (device); [count] = bytes written
+    u32 count;
+    u32 level;
+};
+size_t k0_docs_bytes(u64 in_len, u32 count, u32 cap);
+void k0_docs_carve(K0Buf& K, K0Docs& D, const u8* d_in, const u64* d_off, u64 in_len, u32 count, u32 cap, void* ws);
+int k0_docs_check(const u64* d_off, u32 count, u64* d_res, hipStream_t stream);   // d_res[0] = off[count], d_res[1] != 0: the offsets decrease somewhere
+int k0_docs_prepass(K0Buf K, K0Docs D, u32 cap, hipStream_t stream);             // tile scans + per-document block chains: *K.nBlocks, blk*, D.docFirst, D.blkDoc
+int k5_docs_begin(Pipe P, K5Docs D, hipStream_t stream);                          // resets the cursor; the streams of the empty documents in front of the first block
+int k5_docscan_run(Pipe P, K5Docs D, u32 first_block, hipStream_t stream);        // k5_blockscan's sibling: bit offsets, stream headers and trailers of a sub-batch
+
+int k5_run(Pipe P, u32 max_n, hipStream_t stream, hipEvent_t after = nullptr, hipEvent_t done = nullptr, hipEvent_t crc_ready = nullptr,
+           const K5Docs* docs = nullptr, u32 first_block = 0);   // crc_ready: the block CRCs were computed on another stream (k0_batch); docs: the batch path's cursor kernel instead of k5_blockscan
 int k5_stream_begin(Pipe P, int level, hipStream_t stream, bool zero = true);   // zero = false: the caller has zeroed P.out (on another stream, next to the pre-pass)
 int k5_stream_end(Pipe P, hipStream_t stream);
 int k5_shift_bits_run(const u8* d_in, u64 nbytes, u32 s, u8* d_out, hipStream_t stream);

@@ -27,6 +27,24 @@ int64_t cjs_bz2_compress(cjs_ctx* ctx, const uint8_t* in, uint64_t in_len, int l
 /* The same with input and output resident in HBM (device pointers, d_out 4-byte aligned). */
 int64_t cjs_bz2_compress_device(cjs_ctx* ctx, const void* d_in, uint64_t in_len, int level, void* d_out,
                                 uint64_t out_cap);
+/* Batched form: `count` independent documents in, one complete .bz2 stream each out, in ONE trip through the kernels.
+ * The reference has no batched entry; the contract is "equal to N single calls": stream d is bit-identical to what
+ * Bzip2.compressFile (lib/Bzip2.js:879-929) gives for document d alone - its blocks are the ones readBlock (:636-667)
+ * cuts from that document (a document start starts a fresh block and a fresh run), its stream header (:903-906),
+ * combined CRC (:917) and trailer (:925-927) are its own.  Documents are packed back to back: document d is input bytes
+ * [off[d], off[d+1]), off = count + 1 nondecreasing offsets; empty documents are allowed (a 14-byte stream); one level for
+ * the call.  Stream d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0, byte-aligned and back to back without padding -
+ * the whole output is also a valid multi-stream .bz2 file (cjs_bz2_decompress with multistream != 0 decodes it).
+ * Both return the total number of bytes written (count == 0: 0), or CJS_E_LEVEL, CJS_E_ARG (null pointers, decreasing
+ * offsets, d_out not 4-byte aligned, and - as in cjs_bz2_compress_device - a d_out of fewer than 64 bytes), CJS_E_NOSPACE
+ * (out_cap too small for the streams; cjs_bz2_compress_batch_bound is enough),
+ * CJS_E_NOGPU, -100-hipError_t.  The device form takes device pointers throughout (d_off and d_out_off included); the host
+ * form uploads once and downloads once.  cjs_last_device_ms / cjs_last_block_count report the batch call. */
+int64_t cjs_bz2_compress_batch_bound(uint64_t total_len, uint32_t count);
+int64_t cjs_bz2_compress_batch_device(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, int level,
+                                      void* d_out, uint64_t out_cap, uint64_t* d_out_off);
+int64_t cjs_bz2_compress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, int level,
+                               uint8_t* out, uint64_t out_cap, uint64_t* out_off);
 /* = BWTC.compressFile(input, null, level) for level 6..9   (reference: lib/BWTC.js:12-139,
  * lib/Util.js:105-142).  GPU: BWT.bwtransform + MTF + RLE2 per 100000*level-byte block; host: the
  * adaptive Fenwick model + range coder (serial by construction: lib/RangeCoder.js, lib/FenwickModel.js).

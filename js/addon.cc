@@ -2,6 +2,7 @@
 // (include/compressjs_amd.h).  Built by plain g++ (no node-gyp): see __graft_entry__.build_addon().
 //
 //   compress(input: Buffer|Uint8Array, level: number) -> Buffer      = Bzip2.compressFile hot path
+//   compressMany(inputs: (Buffer|Uint8Array)[], level: number) -> Buffer[]   many independent inputs in one call
 //   bwtransform2(T: Uint8Array, U: Uint8Array, n: number) -> pidx     = BWT.bwtransform2
 //
 // The shared library is dlopen()ed at require() time from ../compressjs_amd/ (or
@@ -22,6 +23,8 @@ static cjs_ctx* (*p_create)(int, uint32_t);
 static void (*p_destroy)(cjs_ctx*);
 static int64_t (*p_bound)(uint64_t);
 static int64_t (*p_compress)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t);
+static int64_t (*p_batch_bound)(uint64_t, uint32_t);
+static int64_t (*p_compress_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*);
 static int64_t (*p_compress_multi)(cjs_ctx**, uint32_t, const uint8_t*, uint64_t, int, uint8_t*, uint64_t);
 static int32_t (*p_device_count)(void);
 static int32_t (*p_bwt)(const uint8_t*, uint8_t*, uint32_t, uint32_t*);
@@ -58,6 +61,8 @@ static bool load_lib(const char* path) {
     p_bound = (int64_t(*)(uint64_t))dlsym(g_lib, "cjs_bz2_compress_bound");
     p_compress = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bz2_compress");
     p_compress_multi = (int64_t(*)(cjs_ctx**, uint32_t, const uint8_t*, uint64_t, int, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bz2_compress_multi");
+    p_batch_bound = (int64_t(*)(uint64_t, uint32_t))dlsym(g_lib, "cjs_bz2_compress_batch_bound");
+    p_compress_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*))dlsym(g_lib, "cjs_bz2_compress_batch");
     p_device_count = (int32_t(*)(void))dlsym(g_lib, "cjs_device_count");
     p_bwt = (int32_t(*)(const uint8_t*, uint8_t*, uint32_t, uint32_t*))dlsym(g_lib, "cjs_bwt_cyclic");
     p_bwtlin = (int32_t(*)(const uint8_t*, uint8_t*, uint32_t, uint32_t*))dlsym(g_lib, "cjs_bwt_linear");
@@ -75,7 +80,7 @@ static bool load_lib(const char* path) {
     p_bwtc_fetch = (int64_t(*)(cjs_ctx*, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bwtc_fetch");
     p_bwtc_bound = (int64_t(*)(uint64_t))dlsym(g_lib, "cjs_bwtc_compress_bound");
     p_bwtc = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t))dlsym(g_lib, "cjs_bwtc_compress");
-    if (!p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound) { g_err = "missing symbols"; return false; }
+    if (!p_batch_bound || !p_compress_batch || !p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound) { g_err = "missing symbols"; return false; }
     return true;
 }
 
@@ -257,6 +262,48 @@ static napi_value Compress(napi_env env, napi_callback_info info) {
         napi_adjust_external_memory(env, blk->accounted, &now);
     }
     return out;
+}
+
+// compressMany(buffers: (Buffer|Uint8Array)[], level) -> Buffer[]   one .bz2 stream per input, each what compress() gives for it alone
+// (cjs_bz2_compress_batch: one upload, one trip through the kernels, one download).  With several devices configured the batch
+// runs on the first one's context.
+static napi_value CompressMany(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    bool isarr = false;
+    if (argc < 2 || napi_is_array(env, argv[0], &isarr) != napi_ok || !isarr) { napi_throw_type_error(env, nullptr, "compressMany(buffers, level)"); return nullptr; }
+    int32_t level = 9;
+    napi_get_value_int32(env, argv[1], &level);
+    if (level < 1 || level > 9) return throw_code(env, -20, "compressMany");
+    uint32_t count = 0;
+    napi_get_array_length(env, argv[0], &count);
+    std::vector<uint64_t> off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
+    std::vector<uint8_t*> ptr(count);
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value v; size_t len = 0;
+        napi_get_element(env, argv[0], i, &v);
+        if (!get_bytes(env, v, &ptr[i], &len)) { napi_throw_type_error(env, nullptr, "compressMany(buffers, level): every input must be a Buffer or Uint8Array"); return nullptr; }
+        off[i + 1] = off[i] + len;
+    }
+    napi_value arr;
+    napi_create_array_with_length(env, count, &arr);
+    if (!count) return arr;
+    if (!ensure_ctx(env)) return nullptr;
+    const uint64_t total = off[count], cap = (uint64_t)p_batch_bound(total, count);
+    std::vector<uint8_t> flat((size_t)(total ? total : 1));
+    for (uint32_t i = 0; i < count; i++) if (off[i + 1] > off[i]) memcpy(flat.data() + off[i], ptr[i], (size_t)(off[i + 1] - off[i]));
+    StageBlock* blk = stage_take(cap);
+    if (!blk) { napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+    const int64_t n = p_compress_batch(g_ctx, flat.data(), off.data(), count, level, blk->data, cap, out_off.data());
+    if (n < 0) { stage_give(blk); return throw_code(env, n, "cjs_bz2_compress_batch"); }
+    if ((uint64_t)n > blk->hw) blk->hw = (uint64_t)n;
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value b; void* dst;
+        napi_create_buffer_copy(env, (size_t)(out_off[i + 1] - out_off[i]), blk->data + out_off[i], &dst, &b);
+        napi_set_element(env, arr, i, b);
+    }
+    stage_give(blk);
+    return arr;
 }
 
 static napi_value Bwt2(napi_env env, napi_callback_info info) {
@@ -483,6 +530,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"load", nullptr, Load, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"lastError", nullptr, LastError, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"compress", nullptr, Compress, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"compressMany", nullptr, CompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtransform2", nullptr, Bwt2, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtransform", nullptr, BwtLinear, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"unbwtransform", nullptr, UnBwtLinear, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -2,6 +2,7 @@
 // main.js:4-28 for the functions on the accelerated path.
 //
 //   Bzip2.compressFile(input, [output], [level])   -> MI355X (N-API addon -> C ABI -> HIP kernels)
+//   Bzip2.compressFiles(inputs, [level])           -> MI355X, many independent inputs in one call (not in the reference)
 //   BWT.bwtransform2(T, U, n, [alphabetSize])       -> MI355X
 //   BWT.bwtransform / suffixsort / unbwtransform, BWTC.compressFile (levels 6-9) -> MI355X
 //   Bzip2.decompressFile / decompressBlock / table   -> MI355X (GPU decoder K7-K9)
@@ -64,6 +65,18 @@ Bzip2.compressFile = function(inStream, outStream, props) {          // lib/Bzip
   if (level < 1 || level > 9) throw new Error('Invalid block size multiplier');   // :888-890
   need();
   return deliver(addon.compress(inputBytes(inStream), level), outStream);
+};
+// Not in the reference: many independent inputs in one call, one .bz2 stream each - [compressFile(x, null, level) for every x],
+// bit for bit, in one trip through the GPU (cjs_bz2_compress_batch).  Returns an array of exact-length Uint8Arrays.  With
+// several devices configured the batch runs on the first one.
+Bzip2.compressFiles = function(inputs, props) {
+  var level = 9;
+  if (typeof props === 'number') level = props;
+  if (level < 1 || level > 9) throw new Error('Invalid block size multiplier');   // lib/Bzip2.js:888-890
+  need();
+  var bufs = [];
+  for (var i = 0; i < inputs.length; i++) bufs.push(inputBytes(inputs[i]));
+  return addon.compressMany(bufs, level).map(function(b) { return deliver(b, null); });
 };
 Bzip2.decompressFile = function(input, output, multistream) {       // lib/Bzip2.js:454,931 (Bunzip.decode)
   need();
