@@ -18,7 +18,7 @@ SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_devic
            "cjs_last_device_ms", "cjs_last_block_count", "cjs_stream", "cjs_profile_enable",
            "cjs_profile_read", "cjs_profile_read_class", "cjs_bwt_cyclic", "cjs_bwt_cyclic_batch", "cjs_bwt_linear",
            "cjs_suffixsort", "cjs_unbwt_linear", "cjs_huff_lengths", "cjs_huff_lengths_batch",
-           "cjs_bz2_decompress", "cjs_bz2_decompress_device", "cjs_bz2_decompress_block", "cjs_bz2_table",
+           "cjs_bz2_decompress", "cjs_bz2_decompress_device", "cjs_bz2_decompress_batch", "cjs_bz2_decompress_batch_device", "cjs_dbg_dec_syncs", "cjs_bz2_decompress_block", "cjs_bz2_table",
            "cjs_bz2_last_size", "cjs_bz2_fetch", "cjs_shift_bits", "cjs_bwtc_decompress", "cjs_bwtc_last_size", "cjs_bwtc_fetch", "cjs_bz2_last_detail", "cjs_bz2_last_decode_ms",
            "cjs_dbg_bwt_batch_time", "cjs_dbg_block_stages", "cjs_dbg_k1_sparse_rounds",
            "cjs_dbg_k1_rounds", "cjs_dbg_k1_periodic_blocks", "cjs_dbg_rc_div", "cjs_dbg_multi_mallocs", "cjs_dbg_multi_fallbacks", "cjs_dbg_multi_replans"]
@@ -124,6 +124,13 @@ def load(path: str | None = None):
     L.cjs_bz2_decompress.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int]
     L.cjs_bz2_decompress_device.restype = C.c_int64
     L.cjs_bz2_decompress_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int]
+    if hasattr(L, "cjs_bz2_decompress_batch"):   # (as for cjs_bz2_compress_batch above: absent from an older library loaded for A/B timing)
+        L.cjs_bz2_decompress_batch.restype = C.c_int64
+        L.cjs_bz2_decompress_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp, vp]
+        L.cjs_bz2_decompress_batch_device.restype = C.c_int64
+        L.cjs_bz2_decompress_batch_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp, vp]
+        L.cjs_dbg_dec_syncs.restype = C.c_int
+        L.cjs_dbg_dec_syncs.argtypes = []
     L.cjs_bz2_decompress_block.restype = C.c_int64
     L.cjs_bz2_decompress_block.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     L.cjs_bz2_table.restype = C.c_int64
@@ -156,18 +163,23 @@ DECODE_MESSAGES = {-1: "Bad file checksum", -2: "Not bzip data", -3: "Unexpected
                    -5: "Data error", -6: "Out of memory", -7: "Obsolete (pre 0.9.5) bzip format not supported."}
 
 
+def decode_error(rc: int, d: int, got: int, want: int) -> TypeError:
+    """What the reference's _throw(status, optDetail) raises for a decoder code and the detail numbers of cjs_bz2_last_detail."""
+    detail = {1: "bad magic", 2: "level out of range", 3: "initial position out of bounds",
+              4: "Bad block CRC (got %x expected %x)" % (got, want),
+              5: "Bad stream CRC (got %x expected %x)" % (got, want)}.get(d)
+    err = TypeError(DECODE_MESSAGES[rc] + (": " + detail if detail else ""))
+    err.errorCode = rc
+    return err
+
+
 def raise_decode_error(L, h, rc: int):
     """Raise what the reference's _throw(status, optDetail) raises for a negative decoder code."""
     if rc not in DECODE_MESSAGES:
         check(rc, "cjs_bz2_decompress")
     got, want = C.c_uint32(0), C.c_uint32(0)
     d = L.cjs_bz2_last_detail(h, C.byref(got), C.byref(want))
-    detail = {1: "bad magic", 2: "level out of range", 3: "initial position out of bounds",
-              4: "Bad block CRC (got %x expected %x)" % (got.value, want.value),
-              5: "Bad stream CRC (got %x expected %x)" % (got.value, want.value)}.get(d)
-    err = TypeError(DECODE_MESSAGES[rc] + (": " + detail if detail else ""))
-    err.errorCode = rc
-    raise err
+    raise decode_error(rc, d, got.value, want.value)
 
 
 def check(rc: int, what: str = "call") -> int:

@@ -119,6 +119,64 @@ class Context:
             _lib.raise_decode_error(self.L, self.h, int(n))
         return b""
 
+    def decompress_many(self, streams, multistream: bool = False, return_errors: bool = False) -> list:
+        """Many independent .bz2 documents in one call (cjs_bz2_decompress_batch): entry d is decompress(streams[d], multistream).
+        A document that fails raises what decompress would raise for it, with .index = d (the first failing one) - or, with
+        return_errors, that exception instance takes its place in the list and the other documents are still delivered."""
+        arrs = [_coerce_input(s).reshape(-1) for s in streams]
+        if not arrs:
+            return []
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        out_off = np.zeros(count + 1, dtype=np.uint64)
+        status = np.zeros(count, dtype=np.int32)
+        detail = np.zeros(3 * count, dtype=np.uint32)
+        out = self._staging(1)
+        n = self.L.cjs_bz2_decompress_batch(self.h, flat.ctypes.data, off.ctypes.data, count, int(bool(multistream)), out.ctypes.data,
+                                            0, out_off.ctypes.data, status.ctypes.data, detail.ctypes.data)
+        if n == -21:                                   # sizes now known: fetch the retained result
+            n = int(self.L.cjs_bz2_last_size(self.h))
+            out = self._staging(max(n, 1))
+            n = self.L.cjs_bz2_fetch(self.h, out.ctypes.data, n)
+        _lib.check(n, "cjs_bz2_decompress_batch")
+        res = []
+        for k in range(count):
+            if status[k]:
+                err = _lib.decode_error(int(status[k]), int(detail[3 * k]), int(detail[3 * k + 1]), int(detail[3 * k + 2]))
+                err.index = k
+                if not return_errors:
+                    raise err
+                res.append(err)
+            else:
+                res.append(out[int(out_off[k]):int(out_off[k + 1])].tobytes())
+        return res
+
+    def decompress_many_device(self, d_in, d_off, d_out, d_out_off, d_status, multistream: bool = False, d_detail=None) -> int:
+        """The same with everything resident in HBM: d_in / d_out torch uint8 CUDA tensors, d_off / d_out_off 64-bit integer CUDA
+        tensors of count + 1 elements, d_status an int32 CUDA tensor of count elements (0 or the reference's Err code of document
+        d; a failed document contributes no bytes), d_detail an optional 32-bit CUDA tensor of 3 * count elements.  Returns the
+        total number of decoded bytes."""
+        import torch
+        count = int(d_off.numel()) - 1
+        i64 = (torch.int64, getattr(torch, "uint64", torch.int64))
+        i32 = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for name, t, dt in (("d_in", d_in, (torch.uint8,)), ("d_out", d_out, (torch.uint8,)), ("d_off", d_off, i64),
+                            ("d_out_off", d_out_off, i64), ("d_status", d_status, (torch.int32,)), ("d_detail", d_detail, i32)):
+            if t is None and name == "d_detail":
+                continue
+            if t.dtype not in dt or not t.is_contiguous():
+                raise ValueError("%s: a contiguous tensor of dtype %s" % (name, dt[0]))
+            if t.device != d_in.device:
+                raise ValueError("%s: on another device than d_in" % name)
+        if count < 0 or d_out_off.numel() < count + 1 or d_status.numel() < count or (d_detail is not None and d_detail.numel() < 3 * count):
+            raise ValueError("d_off / d_out_off: count + 1 elements, d_status: count, d_detail: 3 * count")
+        n = self.L.cjs_bz2_decompress_batch_device(self.h, d_in.data_ptr(), d_off.data_ptr(), count, int(bool(multistream)),
+                                                   d_out.data_ptr(), d_out.numel(), d_out_off.data_ptr(), d_status.data_ptr(),
+                                                   d_detail.data_ptr() if d_detail is not None else None)
+        return _lib.check(n, "cjs_bz2_decompress_batch_device")
+
     def decompress_block(self, stream, bitpos: int) -> bytes:
         """Bzip2.decompressBlock (lib/Bzip2.js:482-503)."""
         d = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -328,6 +386,12 @@ class Bzip2:
         """Bzip2.decompressFile = Bunzip.decode (lib/Bzip2.js:454-481) on the GPU decoder (K7-K9)."""
         data = _coerce_input(inStream)
         return _deliver(default_context().decompress(data, multistream), outStream)
+
+    @staticmethod
+    def decompressFiles(inputs, multistream=False, return_errors=False):
+        """Many independent .bz2 inputs in one trip through the GPU (the reference has no batched entry):
+        [Bzip2.decompressFile(x, None, multistream) for x in inputs]; a document that fails raises its error with .index set."""
+        return default_context().decompress_many([_coerce_input(x) for x in inputs], multistream, return_errors)
 
     @staticmethod
     def decompressBlock(inStream, bitPos, outStream=None):

@@ -407,6 +407,7 @@ static int64_t dec_deliver(cjs_ctx* c, int64_t n, uint8_t* out, uint64_t out_cap
     u64 sz = 0;
     const u8* d = dec_output(c->dec, &sz);
     hipError_t e = hipMemcpyAsync(out, d, (size_t)n, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
+    dec_sync_note();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return e == hipSuccess ? n : (int64_t)(CJS_E_HIP - (int)e);
 }
@@ -469,3 +470,31 @@ extern "C" int32_t cjs_bz2_last_detail(cjs_ctx* c, uint32_t* crc_got, uint32_t* 
     return d;
 }
 extern "C" float cjs_bz2_last_decode_ms(cjs_ctx* c) { return c ? c->dec_ms : 0.f; }
+extern "C" int cjs_dbg_dec_syncs(void) { return dec_sync_count(); }
+
+// Batched form (declared in include/compressjs_amd.h): document d decodes as Bzip2.decompressFile (lib/Bzip2.js:454-481) does on it
+// alone; the document level is in decode.hip (dec_batch) and k7_docs.hip.
+static int64_t dec_batch_call(cjs_ctx* c, const uint8_t* in, const uint64_t* off, uint32_t count, int multistream, uint8_t* out,
+                              uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail, bool dev) {
+    if (!c) return CJS_E_ARG;
+    if (count == 0) return 0;
+    if (!off || !out_off || !status) return CJS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return CJS_E_NOGPU;
+    (void)hipEventRecord(c->ev0, c->stream);
+    const int64_t n = dec_batch(&c->dec, dec_slots(c), c->stream, in, (const u64*)off, count, dev, multistream, (u64*)out_off, status, detail);
+    (void)hipEventRecord(c->ev1, c->stream);
+    dec_sync_note();
+    (void)hipStreamSynchronize(c->stream);
+    c->dec_ms = 0.f;
+    (void)hipEventElapsedTime(&c->dec_ms, c->ev0, c->ev1);
+    return dec_deliver(c, n, out, out_cap, dev);
+}
+extern "C" int64_t cjs_bz2_decompress_batch(cjs_ctx* c, const uint8_t* in, const uint64_t* off, uint32_t count, int multistream,
+                                            uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail) {
+    return dec_batch_call(c, in, off, count, multistream, out, out_cap, out_off, status, detail, false);
+}
+extern "C" int64_t cjs_bz2_decompress_batch_device(cjs_ctx* c, const uint8_t* d_in, const uint64_t* d_off, uint32_t count, int multistream,
+                                                   uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status,
+                                                   uint32_t* d_detail) {
+    return dec_batch_call(c, d_in, d_off, count, multistream, d_out, out_cap, d_out_off, d_status, d_detail, true);
+}

@@ -62,7 +62,26 @@ struct DecBuf {
     const u64* outOff;   // [nvalid] offset of its decoded bytes in `out`
     u8* out;
     u32* crcOut;         // [nvalid] CRC of the decoded bytes
+    // a batch of documents (k7_docs.hip); null for a single stream
+    const u32* candLim;  // [slots] first 256-byte chunk behind the candidate's document: the block reads zeros from there on
 };
+
+// a batch of documents (k7_docs.hip)
+struct DecCand {         // one magic found by k7_scan_docs
+    u64 key;             // (bit position in the staged batch << 1) | 1 for the end-of-stream magic
+    u32 a, b;            // block: a = first chunk behind its document; end of stream: a = the stream CRC behind it, b = the 4 bytes at the next byte boundary
+};
+struct DecDocRec {       // outcome of one document, as k9_docs_meta / k9_docs_gather read it
+    u64 src, dst;        // where its decoded bytes lie in the decoder's buffer / in the result
+    int status;          // 0 or the reference's Err code
+    u32 detail, got, want;
+};
+int k7_stage(const u8* d_in, const u64* d_off, const u64* d_base, u32 count, u64 staged, u8* d_st, u32* d_chunkDoc, u32* d_head,
+             hipStream_t stream);
+int k7_scan_batch(const u8* d_st, u64 staged, const u64* d_off, const u64* d_base, const u32* d_chunkDoc, DecCand* d_cand,
+                  u32* d_ncand, u32 cap, hipStream_t stream);
+int k9_docs_finish(const DecDocRec* d_rec, u32 count, u64* d_out_off, int* d_status, u32* d_detail, hipStream_t stream);
+int k9_docs_compact(const DecDocRec* d_rec, u32 count, const u8* d_src, u8* d_dst, u64 total, hipStream_t stream);
 
 int k7_scan(const u8* d_in, u64 len, u64 first_bit, u64* d_cand, u32* d_ncand, u32 cap, hipStream_t stream);
 int k7_run(DecBuf D, u32 first, u32 count, hipStream_t stream);

@@ -9,6 +9,14 @@ int64_t dec_stream(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 l
                    bool check_stream_crc);
 // Bunzip.decodeBlock on a host buffer
 int64_t dec_block(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 len, u64 bitpos);
+// a batch of documents (cjs_bz2_decompress_batch): document d = in[off[d], off[d+1]) decodes as dec_stream does on it alone.  dev:
+// in / off / out_off / status / detail are device pointers.  Returns the total of decoded bytes (they stay in the decoder's buffer,
+// failed documents contributing none) or a call-level error; per-document outcomes go to out_off / status / detail (may be null).
+int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const u64* off, u32 count, bool dev, int multistream,
+                  u64* out_off, int* status, u32* detail);
+// host<->device synchronisations of the last decode call (dec_sync_note: one more, made by the caller on its behalf)
+int dec_sync_count();
+void dec_sync_note();
 const u8* dec_output(DecState* S, u64* size);
 void dec_error_info(DecState* S, int* detail, u32* got, u32* want);
 u32 dec_table(DecState* S, const u64** pos, const u64** size);

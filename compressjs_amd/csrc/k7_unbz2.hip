@@ -49,13 +49,14 @@ __global__ __launch_bounds__(256) void k7_scan_magic(const u8* in, u64 len, u64 
 struct BitRd {
     const u32* w;      // 4-byte aligned stream
     u64 zeroChunk;     // a chunk that lies entirely in the zero padding behind the stream
+    u64 lim;           // chunks from this one on read as zeros (the single stream: zeroChunk itself; a batch: where the block's document ends)
     u32 ca, cb;        // this lane's word of the current chunk (MSB first) and of the next one (raw)
     u64 win;           // next unread bits, MSB aligned
     int avail;         // valid bits in win
     u64 next;          // index of the next word to append to win
 };
 __device__ __forceinline__ u32 br_load(const BitRd& r, u64 chunk) {
-    const u64 c = chunk < r.zeroChunk ? chunk : r.zeroChunk;      // unconditional load: nothing waits on it here
+    const u64 c = chunk < r.lim ? chunk : r.zeroChunk;      // unconditional load: nothing waits on it here
     return r.w[c * 64u + lane_id()];
 }
 __device__ __forceinline__ u32 br_word(BitRd& r) {
@@ -64,8 +65,8 @@ __device__ __forceinline__ u32 br_word(BitRd& r) {
     r.next++;
     return (u32)__builtin_amdgcn_readlane((int)r.ca, (int)k);
 }
-__device__ __forceinline__ void br_init(BitRd& r, const u32* w, u64 zeroChunk, u64 bitpos) {
-    r.w = w; r.zeroChunk = zeroChunk;
+__device__ __forceinline__ void br_init(BitRd& r, const u32* w, u64 zeroChunk, u64 lim, u64 bitpos) {
+    r.w = w; r.zeroChunk = zeroChunk; r.lim = lim;
     r.next = bitpos >> 5;
     const u64 chunk = r.next >> 6;
     r.cb = br_load(r, chunk);
@@ -210,7 +211,11 @@ __device__ __forceinline__ u32 mtf_step(u32& l0, u32& l1, u32& l2, u32& l3, u32 
 // Rings: A -> B group records (K7_GRING), B -> C, D symbol rows (K7_RROWS), C -> D output bytes in the same slots.  Waits end on
 // the producer's progress or on s_stop / s_abort / s_adone / s_bdone / s_cdone; wave B decides everything that depends on the
 // order of symbols (which error or end-of-block comes first), exactly as the sequential reference would meet them.
-__global__ __launch_bounds__(256) void k7_decode(DecBuf D, u32 first, u32 count) {
+// DOCS: the candidates are blocks of a batch of documents packed into one input buffer (k7_docs.hip): the bit reader of a block
+// reads zeros from D.candLim[candidate] on - the first chunk behind its own document - instead of from D.zeroChunk on, so a
+// truncated document never reads its neighbour.  The single-stream kernel passes zeroChunk for both and compiles as before.
+template <bool DOCS>
+__device__ __forceinline__ void k7_decode_body(const DecBuf& D, u32 first, u32 count) {
     const u32 slot = blockIdx.x;
     if (slot >= count) return;
     const u32 lane = lane_id();
@@ -250,7 +255,7 @@ __global__ __launch_bounds__(256) void k7_decode(DecBuf D, u32 first, u32 count)
     int groupCount = 0;
     if (wave == 0) {
         const u64 start = D.cand[first + slot] >> 1;
-        br_init(r, D.in32, D.zeroChunk, start + 48);
+        br_init(r, D.in32, D.zeroChunk, DOCS ? (u64)D.candLim[first + slot] : D.zeroChunk, start + 48);
         int st = 0;
         const u32 crc = br_get(r, 32);
         u32 origPtr = 0, mw = 0;
@@ -811,6 +816,8 @@ __global__ __launch_bounds__(256) void k7_decode(DecBuf D, u32 first, u32 count)
         D.res[slot] = res;
     }
 }
+__global__ __launch_bounds__(256) void k7_decode(DecBuf D, u32 first, u32 count) { k7_decode_body<false>(D, first, count); }
+__global__ __launch_bounds__(256) void k7_decode_docs(DecBuf D, u32 first, u32 count) { k7_decode_body<true>(D, first, count); }
 
 int k7_scan(const u8* d_in, u64 len, u64 first_bit, u64* d_cand, u32* d_ncand, u32 cap, hipStream_t stream) {
     HIP_CHECK_RET(hipMemsetAsync(d_ncand, 0, 4, stream));
@@ -819,7 +826,8 @@ int k7_scan(const u8* d_in, u64 len, u64 first_bit, u64* d_cand, u32* d_ncand, u
     return CJS_OK;
 }
 int k7_run(DecBuf D, u32 first, u32 count, hipStream_t stream) {
-    hipLaunchKernelGGL(k7_decode, dim3(count), dim3(256), 0, stream, D, first, count);
+    if (D.candLim) hipLaunchKernelGGL(k7_decode_docs, dim3(count), dim3(256), 0, stream, D, first, count);
+    else hipLaunchKernelGGL(k7_decode, dim3(count), dim3(256), 0, stream, D, first, count);
     HIP_CHECK_RET(hipGetLastError());
     return CJS_OK;
 }

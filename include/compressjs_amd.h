@@ -204,6 +204,26 @@ int64_t cjs_bz2_fetch(cjs_ctx* ctx, uint8_t* out, uint64_t out_cap);
 int32_t cjs_bz2_last_detail(cjs_ctx* ctx, uint32_t* crc_got, uint32_t* crc_expected);
 float cjs_bz2_last_decode_ms(cjs_ctx* ctx);
 
+/* Batched form: `count` independent .bz2 documents in, the decoded bytes of each out, in ONE trip through the kernels.  The
+ * reference has no batched entry; the contract is "equal to N single calls": result d is what Bzip2.decompressFile(document d, null,
+ * multistream) (lib/Bzip2.js:454-481) gives for that document ALONE - bits behind its end read as zeros (lib/BitStream.js:84), never
+ * as its neighbour's bytes - either the decoded bytes or the reference's Err code in status[d] (0, or -2 / -5 / -7 as above; which
+ * one, and when, follows the reference's sequential order inside the document: a bad block CRC in block 1 wins over a structural
+ * error behind block 2).  detail[3d .. 3d+2] = optDetail number, CRC got, CRC expected, as cjs_bz2_last_detail reports them
+ * (`detail` may be NULL).  Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, any byte alignment, empty
+ * documents allowed (status -2, detail 1).  Results lie back to back: result d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0;
+ * a failed document contributes no bytes and changes nothing for any other document.
+ * Both return the total number of decoded bytes (>= 0 even when documents failed; count == 0: 0).  Negative returns are call-level
+ * only: CJS_E_ARG (null ctx / off / out_off / status, decreasing offsets, null `in` with a non-empty batch), CJS_E_NOGPU,
+ * -100-hipError_t, CJS_E_UNSUPPORTED (candidate cap), and CJS_E_NOSPACE when out_cap is too small - out_off / status / detail have
+ * been written then and the result stays in HBM (cjs_bz2_last_size / cjs_bz2_fetch).  The device form takes device pointers
+ * throughout.  cjs_bz2_last_decode_ms reports the batch call; cjs_bz2_last_detail is the single call's and reads 0 after a batch. */
+int64_t cjs_bz2_decompress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, int multistream,
+                                 uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail);
+int64_t cjs_bz2_decompress_batch_device(cjs_ctx* ctx, const uint8_t* d_in, const uint64_t* d_off, uint32_t count, int multistream,
+                                        uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, uint32_t* d_detail);
+int cjs_dbg_dec_syncs(void);          /* host<->device synchronisations (stream syncs, synchronous copies) of the last decode call of the process */
+
 /* = BWTC.decompressFile(input, output)   (reference: lib/BWTC.js:141-233 via Util.decompressFileHelper
  *   lib/Util.js:143-166; decoder sides of lib/RangeCoder.js:146-226, lib/FenwickModel.js:88-136,
  *   lib/LogDistanceModel.js:37-44, lib/NoModel.js:22-29).  Range decoder on the host (serial by

@@ -33,6 +33,7 @@ static int32_t (*p_sufsort)(const uint8_t*, int32_t*, uint32_t);
 static int32_t (*p_unbwt)(const uint8_t*, uint8_t*, uint32_t, uint32_t);
 static int32_t (*p_hufflen)(int64_t*, uint32_t, uint32_t);
 static int64_t (*p_dec)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint64_t, int);
+static int64_t (*p_dec_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*);
 static int64_t (*p_decblk)(cjs_ctx*, const uint8_t*, uint64_t, uint64_t, uint8_t*, uint64_t);
 static int64_t (*p_table)(cjs_ctx*, const uint8_t*, uint64_t, int, uint64_t*, uint64_t*, uint32_t);
 static int64_t (*p_lastsize)(cjs_ctx*);
@@ -70,6 +71,7 @@ static bool load_lib(const char* path) {
     p_unbwt = (int32_t(*)(const uint8_t*, uint8_t*, uint32_t, uint32_t))dlsym(g_lib, "cjs_unbwt_linear");
     p_hufflen = (int32_t(*)(int64_t*, uint32_t, uint32_t))dlsym(g_lib, "cjs_huff_lengths");
     p_dec = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint64_t, int))dlsym(g_lib, "cjs_bz2_decompress");
+    p_dec_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*))dlsym(g_lib, "cjs_bz2_decompress_batch");
     p_decblk = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, uint64_t, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bz2_decompress_block");
     p_table = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint64_t*, uint64_t*, uint32_t))dlsym(g_lib, "cjs_bz2_table");
     p_lastsize = (int64_t(*)(cjs_ctx*))dlsym(g_lib, "cjs_bz2_last_size");
@@ -398,12 +400,11 @@ static napi_value HuffLengths(napi_env env, napi_callback_info info) {
     return r;
 }
 
-// Bunzip's _throw(status, optDetail) (lib/Bzip2.js:82-88): TypeError with .errorCode and the reference's text
-static napi_value throw_decode(napi_env env, int64_t rc) {
+// Bunzip's _throw(status, optDetail) (lib/Bzip2.js:82-88): TypeError with .errorCode and the reference's text; null for a code that
+// is not one of Bunzip's
+static napi_value decode_error(napi_env env, int64_t rc, int d, uint32_t got, uint32_t want) {
     const char* base = rc == -2 ? "Not bzip data" : rc == -5 ? "Data error" : rc == -7 ? "Obsolete (pre 0.9.5) bzip format not supported." : nullptr;
-    if (!base) return throw_code(env, rc, "cjs_bz2_decompress");
-    uint32_t got = 0, want = 0;
-    const int d = p_detail(g_ctx, &got, &want);
+    if (!base) return nullptr;
     char msg[200];
     if (d == 1) snprintf(msg, sizeof msg, "%s: bad magic", base);
     else if (d == 2) snprintf(msg, sizeof msg, "%s: level out of range", base);
@@ -416,6 +417,13 @@ static napi_value throw_decode(napi_env env, int64_t rc) {
     napi_create_type_error(env, nullptr, m, &e);
     napi_create_int32(env, (int32_t)rc, &code);
     napi_set_named_property(env, e, "errorCode", code);
+    return e;
+}
+static napi_value throw_decode(napi_env env, int64_t rc) {
+    uint32_t got = 0, want = 0;
+    const int d = p_detail(g_ctx, &got, &want);
+    napi_value e = decode_error(env, rc, d, got, want);
+    if (!e) return throw_code(env, rc, "cjs_bz2_decompress");
     napi_throw(env, e);
     return nullptr;
 }
@@ -458,6 +466,62 @@ static napi_value Decompress(napi_env env, napi_callback_info info) {
     if (argc > 1) napi_get_value_bool(env, argv[1], &ms);
     if (!ensure_ctx(env)) return nullptr;
     return fetch_result(env, p_dec(g_ctx, in, len, nullptr, 0, ms ? 1 : 0));
+}
+// decompressMany(buffers, multistream, returnErrors) -> [Buffer | TypeError]   = [Bzip2.decompressFile(x, null, multistream) for every x] in
+// one call (cjs_bz2_decompress_batch).  A document that fails throws what decompress throws for it, with .index - or, with returnErrors,
+// that error object takes its place in the array.
+static napi_value DecompressMany(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    bool isarr = false, ms = false, keep = false;
+    if (argc < 1 || napi_is_array(env, argv[0], &isarr) != napi_ok || !isarr) { napi_throw_type_error(env, nullptr, "decompressMany(buffers, multistream, returnErrors)"); return nullptr; }
+    if (argc > 1) napi_get_value_bool(env, argv[1], &ms);
+    if (argc > 2) napi_get_value_bool(env, argv[2], &keep);
+    uint32_t count = 0;
+    napi_get_array_length(env, argv[0], &count);
+    std::vector<uint64_t> off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
+    std::vector<uint8_t*> ptr(count);
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value v; size_t len = 0;
+        napi_get_element(env, argv[0], i, &v);
+        if (!get_bytes(env, v, &ptr[i], &len)) { napi_throw_type_error(env, nullptr, "decompressMany(buffers, ...): every input must be a Buffer or Uint8Array"); return nullptr; }
+        off[i + 1] = off[i] + len;
+    }
+    napi_value arr;
+    napi_create_array_with_length(env, count, &arr);
+    if (!count) return arr;
+    if (!ensure_ctx(env)) return nullptr;
+    if (!p_dec_batch) return throw_code(env, -24, "cjs_bz2_decompress_batch");
+    const uint64_t total = off[count];
+    std::vector<uint8_t> flat((size_t)(total ? total : 1));
+    for (uint32_t i = 0; i < count; i++) if (off[i + 1] > off[i]) memcpy(flat.data() + off[i], ptr[i], (size_t)(off[i + 1] - off[i]));
+    std::vector<int32_t> status(count, 0);
+    std::vector<uint32_t> detail((size_t)count * 3, 0);
+    int64_t n = p_dec_batch(g_ctx, flat.data(), off.data(), count, ms ? 1 : 0, nullptr, 0, out_off.data(), status.data(), detail.data());
+    StageBlock* blk = nullptr;
+    if (n == -21) {                                            // decoded; the sizes are known now
+        n = p_lastsize(g_ctx);
+        blk = stage_take((uint64_t)n);
+        if (!blk) { napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+        n = p_fetch(g_ctx, blk->data, (uint64_t)n);
+        if (n >= 0 && (uint64_t)n > blk->hw) blk->hw = (uint64_t)n;
+    }
+    if (n < 0) { if (blk) stage_give(blk); return throw_code(env, n, "cjs_bz2_decompress_batch"); }
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value b; void* dst;
+        if (status[i]) {
+            b = decode_error(env, status[i], (int)detail[3 * (size_t)i], detail[3 * (size_t)i + 1], detail[3 * (size_t)i + 2]);
+            if (!b) { if (blk) stage_give(blk); return throw_code(env, status[i], "cjs_bz2_decompress_batch"); }
+            napi_value idx;
+            napi_create_uint32(env, i, &idx);
+            napi_set_named_property(env, b, "index", idx);
+            if (!keep) { if (blk) stage_give(blk); napi_throw(env, b); return nullptr; }
+        } else if (out_off[i + 1] > out_off[i]) napi_create_buffer_copy(env, (size_t)(out_off[i + 1] - out_off[i]), blk->data + out_off[i], &dst, &b);
+        else napi_create_buffer(env, 0, &dst, &b);
+        napi_set_element(env, arr, i, b);
+    }
+    if (blk) stage_give(blk);
+    return arr;
 }
 // decompressBlock(bytes, bitPos) -> Buffer                        = Bzip2.decompressBlock
 static napi_value DecompressBlock(napi_env env, napi_callback_info info) {
@@ -535,6 +599,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"bwtransform", nullptr, BwtLinear, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"unbwtransform", nullptr, UnBwtLinear, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decompress", nullptr, Decompress, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"decompressMany", nullptr, DecompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decompressBlock", nullptr, DecompressBlock, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"table", nullptr, Table, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtcDecompress", nullptr, BwtcDecompress, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -6,6 +6,7 @@
 //   BWT.bwtransform2(T, U, n, [alphabetSize])       -> MI355X
 //   BWT.bwtransform / suffixsort / unbwtransform, BWTC.compressFile (levels 6-9) -> MI355X
 //   Bzip2.decompressFile / decompressBlock / table   -> MI355X (GPU decoder K7-K9)
+//   Bzip2.decompressFiles(inputs, [multistream], [returnErrors]) -> MI355X, many independent inputs in one call (not in the reference)
 //   BWTC.decompressFile                               -> host range decoder + MI355X inverse BWT
 //   everything else (the other 12 codecs)
 //       -> delegated unchanged to an installed reference package (require('compressjs')), when
@@ -81,6 +82,16 @@ Bzip2.compressFiles = function(inputs, props) {
 Bzip2.decompressFile = function(input, output, multistream) {       // lib/Bzip2.js:454,931 (Bunzip.decode)
   need();
   return deliver(addon.decompress(inputBytes(input), !!multistream), output);
+};
+// Not in the reference: many independent .bz2 inputs in one call - [decompressFile(x, null, multistream) for every x] in one trip
+// through the GPU (cjs_bz2_decompress_batch).  Returns an array of Buffers.  An input that fails throws what decompressFile throws
+// for it (same constructor, errorCode and message) with .index set - or, with returnErrors, that error takes its place in the array
+// and the other inputs are still delivered.
+Bzip2.decompressFiles = function(inputs, multistream, returnErrors) {
+  need();
+  var bufs = [];
+  for (var i = 0; i < inputs.length; i++) bufs.push(inputBytes(inputs[i]));
+  return addon.decompressMany(bufs, !!multistream, !!returnErrors);
 };
 Bzip2.decompressBlock = function(input, bitPos, output) {            // lib/Bzip2.js:482,932
   need();
