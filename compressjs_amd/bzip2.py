@@ -106,6 +106,41 @@ class Context:
         _lib.check(n, "cjs_bwtc_compress")
         return out[:n].tobytes()
 
+    def bwtc_compress_many(self, docs, level: int = 9) -> list:
+        """Many independent inputs in one call (cjs_bwtc_compress_batch): one BWTC stream per document, each equal to
+        bwtc_compress(doc, level).  Levels 6-9 run the range coder on the GPU too, one coder per document."""
+        arrs = [np.ascontiguousarray(d, dtype=np.uint8).reshape(-1) for d in docs]
+        if not arrs:
+            return []
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        cap = int(self.L.cjs_bwtc_compress_batch_bound(int(off[-1]), len(arrs)))
+        out = self._staging(cap)
+        out_off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        n = self.L.cjs_bwtc_compress_batch(self.h, flat.ctypes.data, off.ctypes.data, len(arrs), int(level), out.ctypes.data, cap,
+                                           out_off.ctypes.data)
+        _lib.check(n, "cjs_bwtc_compress_batch")
+        return [out[int(out_off[k]):int(out_off[k + 1])].tobytes() for k in range(len(arrs))]
+
+    def bwtc_compress_many_device(self, d_in, d_off, d_out, d_out_off, level: int = 9) -> int:
+        """The same with everything resident in HBM: tensors as for compress_many_device.  Returns the total number of bytes
+        written."""
+        import torch
+        count = int(d_off.numel()) - 1
+        for name, t, dt in (("d_in", d_in, (torch.uint8,)), ("d_out", d_out, (torch.uint8,)),
+                            ("d_off", d_off, (torch.int64, getattr(torch, "uint64", torch.int64))),
+                            ("d_out_off", d_out_off, (torch.int64, getattr(torch, "uint64", torch.int64)))):
+            if t.dtype not in dt or not t.is_contiguous():
+                raise ValueError("%s: a contiguous tensor of dtype %s" % (name, dt[0]))
+            if t.device != d_in.device:
+                raise ValueError("%s: on another device than d_in" % name)
+        if count < 0 or d_out_off.numel() < count + 1:
+            raise ValueError("d_off / d_out_off: count + 1 elements")
+        n = self.L.cjs_bwtc_compress_batch_device(self.h, d_in.data_ptr(), d_off.data_ptr(), count, int(level),
+                                                  d_out.data_ptr(), d_out.numel(), d_out_off.data_ptr())
+        return _lib.check(n, "cjs_bwtc_compress_batch_device")
+
     def decompress(self, stream, multistream: bool = False) -> bytes:
         """Bzip2.decompressFile on host buffers; raises the reference's TypeError(.errorCode) on bad input."""
         d = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -442,6 +477,14 @@ class BWTC:
         size = data.size if known else -1                                        # lib/Util.js:119-124
         return _deliver(default_context().bwtc_compress(data, level, size), outStream)
 
+    @staticmethod
+    def compressFiles(inputs, props=None):
+        """Many independent inputs, one BWTC stream each, in one call (the reference has no batched entry):
+        [BWTC.compressFile(x, None, props) for x in inputs], bit for bit, each with its size declared."""
+        level = 9
+        if isinstance(props, (int, float)) and not isinstance(props, bool) and 1 <= props <= 9:
+            level = int(props)                                                   # lib/BWTC.js:16-19
+        return default_context().bwtc_compress_many([_coerce_input(x) for x in inputs], level)
 
     @staticmethod
     def decompressFile(inStream, outStream=None):

@@ -338,6 +338,17 @@ int64_t bwtc_end(bwtc_coder* c) {
     return n;
 }
 
+// bwtc_end for a caller that lays streams back to back (cjs_bwtc_compress_batch, levels 1-5): the stream's length also when it
+// did not fit its buffer (*overflow; nothing was written beyond the buffer)
+uint64_t bwtc_end_n(bwtc_coder* c, bool* overflow) {
+    c->rc.encodeFreq(1, 2, 3);
+    c->rc.finish();
+    const uint64_t n = c->out.n;
+    *overflow = c->out.overflow;
+    delete c;
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------------
 // decoder
 // ---------------------------------------------------------------------------------------------

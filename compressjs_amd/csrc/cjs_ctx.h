@@ -126,6 +126,8 @@ struct cjs_ctx {
     u32 plan_blocks = 0;
     float bwtc_times[5] = {};  // last cjs_bwtc_compress: K10 launch ms (first stream), ms until all triples were on the host, coder busy ms, total ms, encodeFreq calls
     hipEvent_t evK10[2] = {};
+    hipEvent_t evB10[CJS_NSTREAMS] = {}, evB11[CJS_NSTREAMS] = {};   // cjs_bwtc_compress_batch: K10 of the last sub-batch on that workspace done; the K11 launch that read it done
+    int bwtc_batch_syncs = 0;  // host<->device synchronisations the last cjs_bwtc_compress_batch* call made itself (K1's own read-backs not counted)
     int scan_level = 0;        // cjs_bz2_plan_scan ran for this level (0: no scan)
     uint64_t scan_total = 0;
     // decoder state (allocated by the first decompress call)

@@ -103,6 +103,46 @@ int k6_unbwt_linear(const u8* dT, u8* dU, u32 n, u32 pidx, void* ws, hipStream_t
 int k2_run(Pipe P, u32 max_n, hipStream_t stream);
 // BWTC levels 6..9: FenwickModel of every block on the GPU -> (sy_f | lt_f << 16, tot_f) per encodeFreq call, [nb][stride] each
 int k10_model_run(Pipe P, u32* sylt, u32* tot, u32* ntri, u32 ostride, u32 ocap, hipStream_t stream);
+// Batched BWTC (cjs_bwtc_compress_batch*, k11_bwtc_coder.hip): document d of the batch is input bytes [off[d], off[d+1]) and becomes a
+// BWTC stream of its own, coded by a range coder of its own on the device.
+struct K11State {      // RangeCoder (lib/RangeCoder.js:27-34) of one document between two launches, and its write cursor
+    u32 low, range, buffer, help, bytecount;
+    u32 acc;           // the bytes of the stream's last, incomplete dword
+    u64 n;             // bytes of the stream so far (beyond the document's bound: counted, not stored)
+};
+#define K11_F_NBLOCKS 0      // flags[]: blocks of the batch
+#define K11_F_MAXLEN 1       //          the longest block
+#define K11_F_BAD 2          //          the plan needs more blocks than it has slots for
+#define K11_F_K10 3          //          K10 gave up on a block (its triples did not fit the rows)
+#define K11_F_SCRATCH 4      //          a stream outgrew its document's bound
+#define K11_F_NOSPACE 5      //          the streams do not fit out_cap
+#define K11_F_WORDS 8
+struct K11Plan {
+    const u8* in;      // the documents, back to back (device)
+    const u64* off;    // [count+1] (device)
+    u32 count;
+    u32 bs;            // level * 100000: bytes per block (lib/BWTC.js:27)
+    u32 level;
+    u32 maxBlocks;
+    u32* docFirst;     // [count+1] first block of document d; [count] = blocks of the batch
+    u64* docScr;       // [count+1] byte offset of document d's stream in scr: exclusive scan of its bound (rounded up to a dword)
+    u32* blkDoc;       // [maxBlocks] document of block k
+    K11State* st;      // [count]
+    u32* scr;          // the streams before they are moved to their places
+    u32* flags;        // [K11_F_WORDS]
+};
+struct K11Sub {        // what a sub-batch's K1 / K2 / K10 left for its blocks [first, first + nb) of the batch
+    u32 first, nb;
+    const u32 *nlen, *pidx, *used, *ntri, *sylt, *tot;
+    u32 ostride;       // u32 per row of sylt / tot (= K10's capacity: the batch path gives it its full rows)
+};
+__host__ __device__ static inline u64 k11_bound(u64 len) { return len + len / 4 + 4096; }                 // = bwtc_bound
+size_t k11_plan_bytes(u64 in_len, u32 count, u32 bs);
+void k11_plan_carve(K11Plan& Q, const u8* d_in, const u64* d_off, u64 in_len, u32 count, int level, void* ws);
+int k11_plan_run(K11Plan Q, hipStream_t stream);                                      // docFirst, docScr, blkDoc, flags; the streams of the empty documents
+int k11_gather_run(K11Plan Q, Pipe P, u32 first, hipStream_t stream);                 // rows of P.T and P.nlen for blocks [first, first + P.g.nb)
+int k11_code_run(K11Plan Q, K11Sub S, hipStream_t stream);
+int k11_finish_run(K11Plan Q, u8* d_out, u64 out_cap, u64* d_out_off, u32 split, hipStream_t stream);   // out_off, then the streams to their places
 int k34_run(Pipe P, hipStream_t stream);
 int k3_alloc_lengths_run(long long* d_arr, const u32* d_off, u32 count, int maxlen, hipStream_t stream);
 // Batched compression (cjs_bz2_compress_batch*): document d of the batch is input bytes [off[d], off[d+1]) and becomes a .bz2 stream of

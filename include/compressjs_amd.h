@@ -58,6 +58,34 @@ int64_t cjs_bwtc_compress(cjs_ctx* ctx, const uint8_t* in, uint64_t in_len, int 
  * [1] = ms until every (sy_f, lt_f, tot_f) triple was on the host, [2] = ms the serial range coder (lib/RangeCoder.js:79-89) was busy,
  * [3] = ms of the whole call, [4] = encodeFreq calls. */
 int cjs_bwtc_last_times(cjs_ctx* ctx, float* out5);
+/* Batched BWTC: `count` independent documents in, one complete BWTC stream each out, in one call.  The reference has no batched
+ * entry; the contract is that of cjs_bz2_compress_batch, "equal to N single calls": stream d is bit-identical to
+ * cjs_bwtc_compress(ctx, doc_d, len_d, level, ..., declared_size = len_d), i.e. to BWTC.compressFile(Buffer, null, level)
+ * (lib/BWTC.js:12-139, lib/Util.js:105-142) on document d alone - its own magic, varint of len_d + 1 and coder start; its blocks
+ * are the ceil(len_d / (level * 100000)) fixed-size pieces of that document (lib/BWTC.js:27), a document start starts a fresh block.
+ * Documents are packed back to back: document d is input bytes [off[d], off[d+1]), off = count + 1 nondecreasing offsets; empty
+ * documents are allowed and give the reference's stream for empty input.  One level for the call; a level outside 1..9 means 9
+ * (lib/BWTC.js:16-19).  Stream d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0, back to back.
+ * Both return the total number of bytes written (count == 0: 0), or CJS_E_ARG (null pointers, decreasing offsets), CJS_E_NOSPACE
+ * (out_cap too small: out_off is written all the same; cjs_bwtc_compress_batch_bound = total_len + total_len / 4 + 4096 * count,
+ * the sum of the single call's bounds, is always enough), CJS_E_NOGPU, -100-hipError_t, and CJS_E_UNSUPPORTED if a block's model
+ * output did not fit the rows the block pipeline has for it (not seen; no bytes rather than wrong ones).  Every byte reported
+ * has been written by the call.  The device form takes device pointers throughout; the host form uploads once and downloads once.
+ * cjs_last_device_ms / cjs_last_block_count report the batch call.
+ * Levels 6-9 (FenwickModel) are the fast path: the range coder runs on the GPU as well, one coder per document
+ * (k11_bwtc_coder.hip: lib/RangeCoder.js:27-140, lib/BWTC.js:42-79,137-138, lib/NoModel.js, lib/LogDistanceModel.js), and the batch
+ * does not touch the host between upload and download; the host waits for the device three times per call, whatever `count`
+ * (cjs_dbg_bwtc_batch_syncs; the block sort's own small read-backs per sub-batch not counted).
+ * Levels 1-5 (DefSumModel, lib/BWTC.js:107) are NOT the fast path: the block stages run batched on the GPU, the model and the
+ * coder on the host, document after document; the device form stages through the host for them. */
+int64_t cjs_bwtc_compress_batch_bound(uint64_t total_len, uint32_t count);
+int64_t cjs_bwtc_compress_batch_device(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, int level,
+                                       void* d_out, uint64_t out_cap, uint64_t* d_out_off);
+int64_t cjs_bwtc_compress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, int level,
+                                uint8_t* out, uint64_t out_cap, uint64_t* out_off);
+int cjs_dbg_bwtc_batch_syncs(cjs_ctx* ctx);      /* host<->device synchronisations the last batch call on ctx made itself */
+/* (tests) floor(range / tot) as the device coder computes it (lib/RangeCoder.js:81): host pointers, n pairs, one tiny kernel */
+int cjs_dbg_rc_div_device(const uint32_t* range, const uint32_t* tot, uint32_t n, uint32_t* out);
 
 /* Sharded encoding for multi-GPU runs (blocks are independent once the RLE1 split is known):
  * cjs_bz2_plan   = the readBlock chain of lib/Bzip2.js:913-922 over the whole (device) input;

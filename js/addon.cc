@@ -24,6 +24,8 @@ static void (*p_destroy)(cjs_ctx*);
 static int64_t (*p_bound)(uint64_t);
 static int64_t (*p_compress)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t);
 static int64_t (*p_batch_bound)(uint64_t, uint32_t);
+static int64_t (*p_bwtc_batch_bound)(uint64_t, uint32_t);
+static int64_t (*p_bwtc_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*);
 static int64_t (*p_compress_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*);
 static int64_t (*p_compress_multi)(cjs_ctx**, uint32_t, const uint8_t*, uint64_t, int, uint8_t*, uint64_t);
 static int32_t (*p_device_count)(void);
@@ -82,7 +84,9 @@ static bool load_lib(const char* path) {
     p_bwtc_fetch = (int64_t(*)(cjs_ctx*, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bwtc_fetch");
     p_bwtc_bound = (int64_t(*)(uint64_t))dlsym(g_lib, "cjs_bwtc_compress_bound");
     p_bwtc = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t))dlsym(g_lib, "cjs_bwtc_compress");
-    if (!p_batch_bound || !p_compress_batch || !p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound) { g_err = "missing symbols"; return false; }
+    p_bwtc_batch_bound = (int64_t(*)(uint64_t, uint32_t))dlsym(g_lib, "cjs_bwtc_compress_batch_bound");
+    p_bwtc_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*))dlsym(g_lib, "cjs_bwtc_compress_batch");
+    if (!p_bwtc_batch_bound || !p_bwtc_batch || !p_compress_batch || !p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound) { g_err = "missing symbols"; return false; }
     return true;
 }
 
@@ -343,6 +347,45 @@ static napi_value BwtcCompress(napi_env env, napi_callback_info info) {
     napi_create_buffer_copy(env, (size_t)n, tmp, &dst, &out);
     free(tmp);
     return out;
+}
+
+// bwtcCompressMany(buffers: (Buffer|Uint8Array)[], level) -> Buffer[]   one BWTC stream per input, each what bwtcCompress(x, level,
+// x.length) gives for it alone (cjs_bwtc_compress_batch: one upload, one download; levels 6-9 code every document on the GPU)
+static napi_value BwtcCompressMany(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    bool isarr = false;
+    if (argc < 2 || napi_is_array(env, argv[0], &isarr) != napi_ok || !isarr) { napi_throw_type_error(env, nullptr, "bwtcCompressMany(buffers, level)"); return nullptr; }
+    int32_t level = 9;
+    napi_get_value_int32(env, argv[1], &level);
+    uint32_t count = 0;
+    napi_get_array_length(env, argv[0], &count);
+    std::vector<uint64_t> off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
+    std::vector<uint8_t*> ptr(count);
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value v; size_t len = 0;
+        napi_get_element(env, argv[0], i, &v);
+        if (!get_bytes(env, v, &ptr[i], &len)) { napi_throw_type_error(env, nullptr, "bwtcCompressMany(buffers, level): every input must be a Buffer or Uint8Array"); return nullptr; }
+        off[i + 1] = off[i] + len;
+    }
+    napi_value arr;
+    napi_create_array_with_length(env, count, &arr);
+    if (!count) return arr;
+    if (!ensure_ctx(env)) return nullptr;
+    const uint64_t total = off[count], cap = (uint64_t)p_bwtc_batch_bound(total, count);
+    std::vector<uint8_t> flat((size_t)(total ? total : 1));
+    for (uint32_t i = 0; i < count; i++) if (off[i + 1] > off[i]) memcpy(flat.data() + off[i], ptr[i], (size_t)(off[i + 1] - off[i]));
+    uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
+    if (!tmp) { napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+    const int64_t n = p_bwtc_batch(g_ctx, flat.data(), off.data(), count, level, tmp, cap, out_off.data());
+    if (n < 0) { free(tmp); return throw_code(env, n, "cjs_bwtc_compress_batch"); }
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value b; void* dst;
+        napi_create_buffer_copy(env, (size_t)(out_off[i + 1] - out_off[i]), tmp + out_off[i], &dst, &b);
+        napi_set_element(env, arr, i, b);
+    }
+    free(tmp);
+    return arr;
 }
 
 // bwtransform(T, U, n) -> pidx                                    = BWT.bwtransform
@@ -606,6 +649,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"huffLengths", nullptr, HuffLengths, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"suffixsort", nullptr, SuffixSort, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtcCompress", nullptr, BwtcCompress, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bwtcCompressMany", nullptr, BwtcCompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"configure", nullptr, Configure, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_default, nullptr},
     };

@@ -5,6 +5,7 @@
 //   Bzip2.compressFiles(inputs, [level])           -> MI355X, many independent inputs in one call (not in the reference)
 //   BWT.bwtransform2(T, U, n, [alphabetSize])       -> MI355X
 //   BWT.bwtransform / suffixsort / unbwtransform, BWTC.compressFile (levels 6-9) -> MI355X
+//   BWTC.compressFiles(inputs, [level])            -> MI355X, many independent inputs in one call (not in the reference)
 //   Bzip2.decompressFile / decompressBlock / table   -> MI355X (GPU decoder K7-K9)
 //   Bzip2.decompressFiles(inputs, [multistream], [returnErrors]) -> MI355X, many independent inputs in one call (not in the reference)
 //   BWTC.decompressFile                               -> host range decoder + MI355X inverse BWT
@@ -175,6 +176,15 @@ BWTC.compressFile = function(inStream, outStream, props) {           // lib/BWTC
   var known = !(inStream && typeof inStream.readByte === 'function') || ('size' in inStream && inStream.size >= 0);
   var bytes = inputBytes(inStream);
   return deliver(addon.bwtcCompress(bytes, level, known ? bytes.length : -1), outStream);   // lib/Util.js:119-124
+};
+// Not in the reference: many independent inputs in one call, one BWTC stream each - [BWTC.compressFile(x, null, level) for every x],
+// bit for bit, each with its size declared (cjs_bwtc_compress_batch; levels 6-9 run one range coder per input on the GPU).
+BWTC.compressFiles = function(inputs, props) {
+  var level = (typeof props === 'number' && props >= 1 && props <= 9) ? props : 9;   // lib/BWTC.js:16-19
+  need();
+  var bufs = [];
+  for (var i = 0; i < inputs.length; i++) bufs.push(inputBytes(inputs[i]));
+  return addon.bwtcCompressMany(bufs, level).map(function(b) { return deliver(b, null); });
 };
 BWTC.decompressFile = function(inStream, outStream) {               // lib/BWTC.js:141
   need();
