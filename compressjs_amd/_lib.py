@@ -22,7 +22,9 @@ SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_devic
            "cjs_bz2_last_size", "cjs_bz2_fetch", "cjs_shift_bits", "cjs_bwtc_decompress", "cjs_bwtc_last_size", "cjs_bwtc_fetch", "cjs_bz2_last_detail", "cjs_bz2_last_decode_ms",
            "cjs_dbg_bwt_batch_time", "cjs_dbg_block_stages", "cjs_dbg_k1_sparse_rounds",
            "cjs_dbg_k1_rounds", "cjs_dbg_k1_periodic_blocks", "cjs_dbg_rc_div", "cjs_dbg_multi_mallocs", "cjs_dbg_multi_fallbacks", "cjs_dbg_multi_replans",
-           "cjs_bwtc_compress_batch_bound", "cjs_bwtc_compress_batch", "cjs_bwtc_compress_batch_device", "cjs_dbg_bwtc_batch_syncs", "cjs_dbg_rc_div_device"]
+           "cjs_bwtc_compress_batch_bound", "cjs_bwtc_compress_batch", "cjs_bwtc_compress_batch_device", "cjs_dbg_bwtc_batch_syncs", "cjs_dbg_rc_div_device",
+           "cjs_bwtc_decompress_batch", "cjs_bwtc_decompress_batch_device", "cjs_dbg_bwtc_dec_batch_syncs", "cjs_dbg_bwtc_dec_batch_fallbacks",
+           "cjs_unbwt_linear_batch"]
 
 
 class CompressjsAmdError(RuntimeError):
@@ -163,6 +165,17 @@ def load(path: str | None = None):
     L.cjs_bwtc_last_size.argtypes = [vp]
     L.cjs_bwtc_fetch.restype = C.c_int64
     L.cjs_bwtc_fetch.argtypes = [vp, vp, C.c_uint64]
+    if hasattr(L, "cjs_bwtc_decompress_batch"):  # (absent from an older library loaded for A/B timing)
+        L.cjs_bwtc_decompress_batch.restype = C.c_int64
+        L.cjs_bwtc_decompress_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+        L.cjs_bwtc_decompress_batch_device.restype = C.c_int64
+        L.cjs_bwtc_decompress_batch_device.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+        L.cjs_dbg_bwtc_dec_batch_syncs.restype = C.c_int
+        L.cjs_dbg_bwtc_dec_batch_syncs.argtypes = [vp]
+        L.cjs_dbg_bwtc_dec_batch_fallbacks.restype = C.c_int
+        L.cjs_dbg_bwtc_dec_batch_fallbacks.argtypes = [vp]
+        L.cjs_unbwt_linear_batch.restype = C.c_int32
+        L.cjs_unbwt_linear_batch.argtypes = [vp, vp, vp, C.c_uint32, vp]
     L.cjs_bz2_last_decode_ms.restype = C.c_float
     L.cjs_bz2_last_decode_ms.argtypes = [vp]
     if path is None:

@@ -249,6 +249,65 @@ class Context:
         _lib.check(n, "cjs_bwtc_decompress")
         return b""
 
+    def bwtc_decompress_many(self, streams, return_errors: bool = False) -> list:
+        """Many independent BWTC streams in one call (cjs_bwtc_decompress_batch): entry d is bwtc_decompress(streams[d]).  Levels 6-9
+        run one range decoder per document on the GPU.  A document that fails raises what bwtc_decompress raises for it, with
+        .index = d (the first failing one) - or, with return_errors, that exception takes its place in the list and the other
+        documents are still delivered."""
+        arrs = [_coerce_input(s).reshape(-1) for s in streams]
+        if not arrs:
+            return []
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        out_off = np.zeros(count + 1, dtype=np.uint64)
+        status = np.zeros(count, dtype=np.int32)
+        out = self._staging(1)
+        n = self.L.cjs_bwtc_decompress_batch(self.h, flat.ctypes.data, off.ctypes.data, count, out.ctypes.data, 0, out_off.ctypes.data,
+                                             status.ctypes.data, None)
+        if n == -21:                                   # sizes now known: fetch the retained result
+            n = int(self.L.cjs_bwtc_last_size(self.h))
+            out = self._staging(max(n, 1))
+            n = self.L.cjs_bwtc_fetch(self.h, out.ctypes.data, n)
+        _lib.check(n, "cjs_bwtc_decompress_batch")
+        res = []
+        for k in range(count):
+            if status[k]:
+                try:
+                    _lib.check(int(status[k]), "cjs_bwtc_decompress")
+                except Exception as err:               # noqa: BLE001 - the single call's exception for this code
+                    err.index = k
+                    if not return_errors:
+                        raise
+                    res.append(err)
+            else:
+                res.append(out[int(out_off[k]):int(out_off[k + 1])].tobytes())
+        return res
+
+    def bwtc_decompress_many_device(self, d_in, d_off, d_out, d_out_off, d_status, d_declared=None) -> int:
+        """The same with everything resident in HBM: d_in / d_out torch uint8 CUDA tensors, d_off / d_out_off 64-bit integer CUDA
+        tensors of count + 1 elements, d_status an int32 CUDA tensor of count elements (0, -30 or -31; a failed document contributes
+        no bytes), d_declared an optional int64 CUDA tensor of count elements (the size every header records, -1: unknown).
+        Returns the total number of decoded bytes."""
+        import torch
+        count = int(d_off.numel()) - 1
+        i64 = (torch.int64, getattr(torch, "uint64", torch.int64))
+        for name, t, dt in (("d_in", d_in, (torch.uint8,)), ("d_out", d_out, (torch.uint8,)), ("d_off", d_off, i64),
+                            ("d_out_off", d_out_off, i64), ("d_status", d_status, (torch.int32,)), ("d_declared", d_declared, (torch.int64,))):
+            if t is None and name == "d_declared":
+                continue
+            if t.dtype not in dt or not t.is_contiguous():
+                raise ValueError("%s: a contiguous tensor of dtype %s" % (name, dt[0]))
+            if t.device != d_in.device:
+                raise ValueError("%s: on another device than d_in" % name)
+        if count < 0 or d_out_off.numel() < count + 1 or d_status.numel() < count or (d_declared is not None and d_declared.numel() < count):
+            raise ValueError("d_off / d_out_off: count + 1 elements, d_status / d_declared: count")
+        n = self.L.cjs_bwtc_decompress_batch_device(self.h, d_in.data_ptr(), d_off.data_ptr(), count, d_out.data_ptr(), d_out.numel(),
+                                                    d_out_off.data_ptr(), d_status.data_ptr(),
+                                                    d_declared.data_ptr() if d_declared is not None else None)
+        return _lib.check(n, "cjs_bwtc_decompress_batch_device")
+
     def decompress_device(self, d_in, d_out, multistream: bool = False) -> int:
         """Stream and output are torch uint8 CUDA tensors; returns the decoded size."""
         n = self.L.cjs_bz2_decompress_device(self.h, d_in.data_ptr(), d_in.numel(), d_out.data_ptr(), d_out.numel(),
@@ -491,6 +550,12 @@ class BWTC:
         """BWTC.decompressFile (lib/BWTC.js:141-233), levels 6-9."""
         return _deliver(default_context().bwtc_decompress(_coerce_input(inStream)), outStream)
 
+    @staticmethod
+    def decompressFiles(inputs, return_errors=False):
+        """Many independent BWTC streams in one call (the reference has no batched entry): [BWTC.decompressFile(x) for x in
+        inputs]; a document that fails raises its error with .index set, or takes its place in the list with return_errors."""
+        return default_context().bwtc_decompress_many([_coerce_input(x) for x in inputs], return_errors)
+
 
 class BWT:
     """compressjs.BWT (lib/BWT.js:302-419): the cyclic transform used by bzip2."""
@@ -512,6 +577,23 @@ class BWT:
         u = np.zeros(max(n, 1), dtype=np.uint8)
         _lib.check(_lib.load().cjs_unbwt_linear(t.ctypes.data, u.ctypes.data, n, int(pidx)), "cjs_unbwt_linear")
         U[:n] = u[:n] if isinstance(U, np.ndarray) else bytes(u[:n])
+
+    @staticmethod
+    def unbwtransform_many(blocks, pidxs):
+        """BWT.unbwtransform of many blocks in one call (cjs_unbwt_linear_batch): -> [bytes], entry k the text of (blocks[k], pidxs[k])."""
+        arrs = [np.ascontiguousarray(np.asarray(b), dtype=np.uint8).reshape(-1) for b in blocks]
+        if not arrs:
+            return []
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([a.size for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        pidx = np.ascontiguousarray(np.asarray(pidxs, dtype=np.uint32))
+        if pidx.size != len(arrs):
+            raise ValueError("one primary index per block")
+        u = np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
+        _lib.check(_lib.load().cjs_unbwt_linear_batch(flat.ctypes.data, off.ctypes.data, pidx.ctypes.data, len(arrs), u.ctypes.data),
+                   "cjs_unbwt_linear_batch")
+        return [u[int(off[k]):int(off[k + 1])].tobytes() for k in range(len(arrs))]
 
     @staticmethod
     def suffixsort(T, SA, n, alphabetSize=256):

@@ -93,6 +93,7 @@ extern "C" void cjs_destroy(cjs_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < 2; i++) if (c->evK10[i]) (void)hipEventDestroy(c->evK10[i]);
     for (int i = 0; i < CJS_NSTREAMS; i++) { if (c->evB10[i]) (void)hipEventDestroy(c->evB10[i]); if (c->evB11[i]) (void)hipEventDestroy(c->evB11[i]); }
+    for (int i = 0; i < 5; i++) (void)hipFree(c->bd[i]);
     k1_prof_destroy(c->prof);
     dec_free(c->dec);
     for (int i = 0; i < 3; i++) c->io[i].stop();

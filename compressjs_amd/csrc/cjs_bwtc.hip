@@ -251,21 +251,38 @@ static int bwtc_on_block(void* user, const uint8_t* T, uint32_t length, uint32_t
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e == hipSuccess ? 0 : CJS_E_HIP - (int)e;
 }
+// the three device buffers of one decode (a 900000-byte block at most), and one stream through bwtc_decode with them: what
+// cjs_bwtc_decompress runs, and the host path of cjs_bwtc_decompress_batch document after document
+int cjs::bwtc_dec_bufs_alloc(BwtcDecBufs& B) {
+    const u32 bs = 900000u;
+    const size_t wsb = (size_t)bs * 20 + ((size_t)(bs + 4095) / 4096) * 1024 + 256;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&B.dT, bs)) != hipSuccess || (e = hipMalloc((void**)&B.dU, bs)) != hipSuccess ||
+        (e = hipMalloc(&B.ws, wsb)) != hipSuccess) return CJS_E_HIP - (int)e;
+    return CJS_OK;
+}
+void cjs::bwtc_dec_bufs_free(BwtcDecBufs& B) {
+    (void)hipFree(B.dT); (void)hipFree(B.dU); (void)hipFree(B.ws);
+    B.dT = B.dU = nullptr; B.ws = nullptr;
+}
+int cjs::bwtc_decode_one(cjs_ctx* c, const BwtcDecBufs& B, const uint8_t* in, uint64_t in_len, int64_t* declared_size, std::vector<u8>& out) {
+    out.clear();
+    BwtcSink k = {c, B.dT, B.dU, B.ws, &out, 0};
+    const int rc = bwtc_decode(in, in_len, declared_size, &k, bwtc_on_block);
+    (void)hipStreamSynchronize(c->stream);
+    if (rc) out.clear();
+    return rc;
+}
 extern "C" int64_t cjs_bwtc_decompress(cjs_ctx* c, const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_cap,
                                        int64_t* declared_size) {
     if (!c || (!in && in_len)) return CJS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return CJS_E_NOGPU;
     c->bwtc_out.clear();
-    BwtcSink k = {c, nullptr, nullptr, nullptr, &c->bwtc_out, 0};
-    const u32 bs = 900000u;
-    const size_t wsb = (size_t)bs * 20 + ((size_t)(bs + 4095) / 4096) * 1024 + 256;
-    int rc = CJS_OK;
-    hipError_t e;
-    if ((e = hipMalloc((void**)&k.dT, bs)) != hipSuccess || (e = hipMalloc((void**)&k.dU, bs)) != hipSuccess ||
-        (e = hipMalloc(&k.ws, wsb)) != hipSuccess) rc = CJS_E_HIP - (int)e;
-    if (!rc) rc = bwtc_decode(in, in_len, declared_size, &k, bwtc_on_block);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(k.dT); (void)hipFree(k.dU); (void)hipFree(k.ws);
+    BwtcDecBufs B;
+    int rc = bwtc_dec_bufs_alloc(B);
+    if (!rc) rc = bwtc_decode_one(c, B, in, in_len, declared_size, c->bwtc_out);
+    else (void)hipStreamSynchronize(c->stream);
+    bwtc_dec_bufs_free(B);
     if (rc) { c->bwtc_out.clear(); return rc; }
     return cjs_bwtc_fetch(c, out, out_cap);
 }

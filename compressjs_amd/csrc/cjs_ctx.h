@@ -133,7 +133,11 @@ struct cjs_ctx {
     // decoder state (allocated by the first decompress call)
     DecState* dec = nullptr;
     float dec_ms = 0.f;
-    std::vector<u8> bwtc_out;   // result of the last cjs_bwtc_decompress
+    std::vector<u8> bwtc_out;   // result of the last cjs_bwtc_decompress (or of a cjs_bwtc_decompress_batch* whose out_cap was too small)
+    // cjs_bwtc_decompress_batch*: [0] the plan's documents and flags, [1] block rows, [2] the scratch (the blocks' last columns),
+    // [3] rows of the batched inverse BWT, [4] its workspace - grow-only, kept across calls
+    void* bd[5] = {}; size_t bd_bytes[5] = {};
+    int bwtc_dec_batch_syncs = 0, bwtc_dec_batch_fallbacks = 0;   // of the last such call: its own host<->device waits; documents on the host path
     BwtcGroupJob bwtc_jobs[2];  // double buffer between the GPU stages and the coder thread of cjs_bwtc_compress
     // the overlapped host path (compress_overlapped): persistent helper threads, copy streams, per-slice events and cursors
     hipStream_t side = nullptr; // the block CRCs of every sub-batch (k0_crc) run here, next to K1
@@ -165,6 +169,11 @@ static inline Pipe stream_pipe(const cjs_ctx* c, void* d_out, uint64_t out_cap) 
 static inline void invalidate_plan(cjs_ctx* c) { c->plan_level = 0; c->plan_blocks = 0; c->scan_level = 0; }
 
 int grow(void** p, size_t* have, size_t need);
+// BWTC decode of one stream (cjs_bwtc.hip): range decoder and models on the host, K6 per block
+struct BwtcDecBufs { u8 *dT = nullptr, *dU = nullptr; void* ws = nullptr; };
+int bwtc_dec_bufs_alloc(BwtcDecBufs& B);
+void bwtc_dec_bufs_free(BwtcDecBufs& B);
+int bwtc_decode_one(cjs_ctx* c, const BwtcDecBufs& B, const uint8_t* in, uint64_t in_len, int64_t* declared_size, std::vector<u8>& out);   // 0, -30, -31 or a call-level error; `out` empty unless 0
 int issue_blocks(cjs_ctx* c, const K0Buf& K, u32 cap, u32 first, u32 count, void* d_out, uint64_t out_cap, const K5Docs* docs = nullptr);   // docs: a batch of documents (cjs_batch.hip)
 int run_sub_batch(cjs_ctx* c, const K0Buf& K, const BatchGeom& g, u32 cap, u32 f, u32 nb, u32 si, void* d_out, uint64_t out_cap,
                   Pipe& P, u32 total_blocks);

@@ -24,17 +24,9 @@
 // the inner nodes level by level.
 #include "pipeline.h"
 
-#define K10_MAXSYM 260
-#define K10_OVERFLOW 0xFFFFFFFFu
+#include "k10_tree.h"
 
-__device__ __forceinline__ void k10_sum_tree(u32* tree, u32 numSyms, u32 lane) {      // lib/FenwickModel.js:167-172
-    // tree[i] = tree[2i] + tree[2i+1] for i = numSyms-1 .. 1: children have a longer bit length, so go level by level
-    for (int bl = 9; bl >= 1; bl--) {
-        const u32 lo = 1u << (bl - 1), hi = (1u << bl) < numSyms ? (1u << bl) : numSyms;
-        for (u32 i = lo + lane; i < hi; i += 64u) tree[i] = tree[2u * i] + tree[2u * i + 1u];
-        __builtin_amdgcn_wave_barrier();
-    }
-}
+#define K10_OVERFLOW 0xFFFFFFFFu
 
 // out: sylt[b][k] = sy_f | lt_f << 16, tot[b][k] = tot_f for the k-th encodeFreq call of block b; ntri[b] = their number.
 // A block emits one triple per symbol PLUS one per escape (a first occurrence, or a symbol whose frequency was scaled down to 0:

@@ -100,6 +100,15 @@ int k0_eval(K0Buf K, u64 pos, hipStream_t stream);
 int k0_phase_plan(K0Buf K, u32 cap, u64 t0, u64 own_len, u32 last, u64 total, hipStream_t stream);   // t0: target of the slice's first boundary (round 6: carried from slice to slice; *K.nBlocks, ((u64*)K.nBlocks)[1] = blocks, the next slice's target)
 
 int k6_unbwt_linear(const u8* dT, u8* dU, u32 n, u32 pidx, void* ws, hipStream_t stream);
+// the same over many blocks in one sequence of launches (no host wait); block k = one K6Blk row
+struct K6Blk {
+    u64 tAt, uAt;      // the block's BWT string at T + tAt, its text at U + uAt (the final place)
+    u64 wsAt;          // its slice of the workspace, in u32 (k6_ws_words(n) of them)
+    u32 n, pidx;       // n >= 1, pidx <= n
+};
+#define K6_GROUP_MAX 65535u   // blocks per call (the grid's y extent)
+size_t k6_ws_words(u32 n);
+int k6_unbwt_batch(const K6Blk* d_B, u32 nblk, u32 max_n, const u8* dT, u8* dU, void* ws, hipStream_t stream);
 int k2_run(Pipe P, u32 max_n, hipStream_t stream);
 // BWTC levels 6..9: FenwickModel of every block on the GPU -> (sy_f | lt_f << 16, tot_f) per encodeFreq call, [nb][stride] each
 int k10_model_run(Pipe P, u32* sylt, u32* tot, u32* ntri, u32 ostride, u32 ocap, hipStream_t stream);
@@ -143,6 +152,34 @@ int k11_plan_run(K11Plan Q, hipStream_t stream);                                
 int k11_gather_run(K11Plan Q, Pipe P, u32 first, hipStream_t stream);                 // rows of P.T and P.nlen for blocks [first, first + P.g.nb)
 int k11_code_run(K11Plan Q, K11Sub S, hipStream_t stream);
 int k11_finish_run(K11Plan Q, u8* d_out, u64 out_cap, u64* d_out_off, u32 split, hipStream_t stream);   // out_off, then the streams to their places
+// Batched BWTC decode (cjs_bwtc_decompress_batch*, k12_bwtc_decoder.hip): document d is a BWTC stream of its own, decoded by a
+// range decoder of its own on the device, ONE WAVE per document.
+#define K12_HOST 1           // K12Doc.status: not the fast path - the host decodes this document (cjs_bwtc_decompress's machinery)
+#define K12_F_SCR 0          // flags[] (u64): bytes of scratch the admitted documents need
+#define K12_F_BLK 1          //                their block rows
+#define K12_F_BAD 2          //                the offsets decrease somewhere, or `in` is null with bytes to read
+#define K12_F_TOTAL 3        //                off[count]
+#define K12_F_WORDS 4
+struct K12Doc {
+    u64 scrAt;         // the document's bytes in the scratch (dword aligned)
+    long long declared;   // the size its header records (-1: none, or the header was not read that far)
+    u32 scrLen;        // = declared: the scratch it gets
+    u32 blk0, blkMax;  // its rows; at most ceil(declared / (level * 100000)) blocks
+    int status;        // 0, -30, -31 or K12_HOST
+    u32 nblk, size;    // (K12) blocks decoded, bytes decoded
+    u32 level, pad;
+};
+struct K12Row { u32 len, pidx, place, pad; };   // one block: its MTF-decoded last column lies at scrAt + place
+struct K12Plan {
+    const u8* in; const u64* off; u32 count;
+    u64 budget;        // bytes of scratch a call may take
+    K12Doc* doc;       // [count]
+    K12Row* row;       // [flags[K12_F_BLK]]
+    u8* scr;
+    u64* flags;        // [K12_F_WORDS]
+};
+int k12_plan_run(K12Plan Q, hipStream_t stream);
+int k12_decode_run(K12Plan Q, hipStream_t stream);
 int k34_run(Pipe P, hipStream_t stream);
 int k3_alloc_lengths_run(long long* d_arr, const u32* d_off, u32 count, int maxlen, hipStream_t stream);
 // Batched compression (cjs_bz2_compress_batch*): document d of the batch is input bytes [off[d], off[d+1]) and becomes a .bz2 stream of

@@ -165,6 +165,11 @@ int32_t cjs_bwt_linear(const uint8_t* T, uint8_t* U, uint32_t n, uint32_t* pidx)
 int32_t cjs_suffixsort(const uint8_t* T, int32_t* SA, uint32_t n);
 /* = BWT.unbwtransform(T, U, LF, n, pidx)                (reference: lib/BWT.js:352-363); list ranking */
 int32_t cjs_unbwt_linear(const uint8_t* T, uint8_t* U, uint32_t n, uint32_t pidx);
+/* The same for `count` blocks in one call (host pointers): block k = T[off[k] .. off[k+1]) with primary index pidx[k], its text
+ * to U[off[k] .. off[k+1]); every block is what cjs_unbwt_linear gives for it alone.  One sequence of launches per group of
+ * blocks (the list-ranking workspace of a group, ~20 bytes per byte, stays inside 512 MiB), no host wait in between; a (T, pidx)
+ * pair that is no BWT gets the reference's literal walk.  CJS_E_ARG: pidx[k] > its block's length, decreasing offsets. */
+int32_t cjs_unbwt_linear_batch(const uint8_t* T, const uint64_t* off, const uint32_t* pidx, uint32_t count, uint8_t* U);
 
 /* = require('compressjs/lib/HuffmanAllocator').allocateHuffmanCodeLengths(array, maxLength)
  *   (reference: lib/HuffmanAllocator.js:199-222, exercised by test/huffman.js): in place, ascending
@@ -263,6 +268,35 @@ int64_t cjs_bwtc_decompress(cjs_ctx* ctx, const uint8_t* in, uint64_t in_len, ui
                             int64_t* declared_size);
 int64_t cjs_bwtc_last_size(cjs_ctx* ctx);
 int64_t cjs_bwtc_fetch(cjs_ctx* ctx, uint8_t* out, uint64_t out_cap);
+/* Batched BWTC decode: `count` independent BWTC streams in, the decoded documents back to back out, in one call.  The reference has
+ * no batched entry; the contract is that of cjs_bz2_decompress_batch and cjs_bwtc_compress_batch, "equal to N single calls":
+ * result d is what cjs_bwtc_decompress(ctx, stream_d, len_d, ...) gives for document d alone, with bwtc_decode's order of checks -
+ * either the decoded bytes (status[d] = 0), or status[d] = -30 (bad magic) / -31 (corrupt or truncated) and no bytes.  A damaged
+ * stream that the single call decodes without error into other bytes comes out as those same bytes.  declared[d] (may be NULL)
+ * is the size recorded in the header where the single call reports it, else -1 (unknown; also: bad magic, a size cut short).
+ * Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, at any byte alignment; empty documents are allowed
+ * (-30).  A read behind a document's end is end-of-input for that document, never its neighbour's bytes.  Result d is
+ * out[out_off[d] .. out_off[d+1]), out_off[0] = 0, back to back; a failed document contributes nothing and changes nothing for
+ * any other.  Both forms return the total of decoded bytes (>= 0 also when documents failed; count == 0: 0).  Negative returns
+ * are call-level only: CJS_E_ARG (null ctx / off / out_off / status, decreasing offsets, null `in` with bytes to read),
+ * CJS_E_NOGPU, -100-hipError_t, and CJS_E_NOSPACE when out_cap is too small (a null `out` counts as out_cap = 0) - then out_off,
+ * status and declared are complete all the same and the result is retained for cjs_bwtc_last_size / cjs_bwtc_fetch, which
+ * otherwise keep serving the single call as before.  The device form takes device pointers throughout.
+ * The fast path - FenwickModel streams (levels 6-9) with their size declared, as the encoder makes them: a plan kernel reads the
+ * headers, one range decoder per document runs on the GPU, one wave each (k12_bwtc_decoder.hip: lib/RangeCoder.js:146-226,
+ * lib/FenwickModel.js:88-172, lib/BWTC.js:172-223), the inverse BWT of all blocks runs batched (k6_unbwt_batch) and writes every
+ * block to its final place.  The host waits for the device three times per call, whatever `count` (cjs_dbg_bwtc_dec_batch_syncs):
+ * for the plan's totals, for the documents' statuses and block rows (out_off is their scan, made on the host), and at the end.
+ * The host path - DefSumModel streams (levels 1-5), no size declared, a document that holds more bytes or blocks than its header
+ * declares, a declared size beyond what is left of the call's scratch budget (512 MiB; the memory a call takes is bounded by it,
+ * never by what a header claims): decoded by the single call's machinery, document after document, same result, no speed claim
+ * (cjs_dbg_bwtc_dec_batch_fallbacks counts them; they add their own waits).  The device form stages these through the host. */
+int64_t cjs_bwtc_decompress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
+                                  uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared);
+int64_t cjs_bwtc_decompress_batch_device(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,
+                                         uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared);
+int cjs_dbg_bwtc_dec_batch_syncs(cjs_ctx* ctx);      /* host<->device waits the last such call on ctx made itself */
+int cjs_dbg_bwtc_dec_batch_fallbacks(cjs_ctx* ctx);  /* documents of the last such call that took the host path */
 
 /* Workload helper (not a compression entry point): bytes [first, first + n) of LCG(N, seed) - SURVEY.md 8(c), BASELINE.json
  * configs[3] "random printable ASCII" - written straight into HBM, so that every GPU of a multi-GPU run fills its own slice. */

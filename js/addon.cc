@@ -45,6 +45,7 @@ static int64_t (*p_bwtc_dec)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint6
 static int64_t (*p_bwtc_lastsize)(cjs_ctx*);
 static int64_t (*p_bwtc_fetch)(cjs_ctx*, uint8_t*, uint64_t);
 static int64_t (*p_bwtc_bound)(uint64_t);
+static int64_t (*p_bwtc_dec_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*);
 static int64_t (*p_bwtc)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t);
 static void* g_lib;
 static cjs_ctx* g_ctx;                       // context on the first configured device: every single-device entry point
@@ -83,10 +84,11 @@ static bool load_lib(const char* path) {
     p_bwtc_lastsize = (int64_t(*)(cjs_ctx*))dlsym(g_lib, "cjs_bwtc_last_size");
     p_bwtc_fetch = (int64_t(*)(cjs_ctx*, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bwtc_fetch");
     p_bwtc_bound = (int64_t(*)(uint64_t))dlsym(g_lib, "cjs_bwtc_compress_bound");
+    p_bwtc_dec_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*))dlsym(g_lib, "cjs_bwtc_decompress_batch");
     p_bwtc = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t))dlsym(g_lib, "cjs_bwtc_compress");
     p_bwtc_batch_bound = (int64_t(*)(uint64_t, uint32_t))dlsym(g_lib, "cjs_bwtc_compress_batch_bound");
     p_bwtc_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*))dlsym(g_lib, "cjs_bwtc_compress_batch");
-    if (!p_bwtc_batch_bound || !p_bwtc_batch || !p_compress_batch || !p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound) { g_err = "missing symbols"; return false; }
+    if (!p_bwtc_batch_bound || !p_bwtc_batch || !p_compress_batch || !p_compress_multi || !p_device_count || !p_create || !p_destroy || !p_bound || !p_compress || !p_bwt || !p_bwtlin || !p_sufsort || !p_unbwt || !p_hufflen || !p_dec || !p_decblk || !p_table || !p_lastsize || !p_fetch || !p_detail || !p_bwtc_dec || !p_bwtc_lastsize || !p_bwtc_fetch || !p_bwtc || !p_bwtc_bound || !p_bwtc_dec_batch) { g_err = "missing symbols"; return false; }
     return true;
 }
 
@@ -614,6 +616,60 @@ static napi_value BwtcDecompress(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// bwtcDecompressMany(buffers, returnErrors) -> [Buffer | Error]   = [BWTC.decompressFile(x) for every x] in one call
+// (cjs_bwtc_decompress_batch; levels 6-9 run one range decoder per input on the GPU).  A document that fails throws what
+// bwtcDecompress throws for it, with .index - or, with returnErrors, that error object takes its place in the array.
+static napi_value BwtcDecompressMany(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    bool isarr = false, keep = false;
+    if (argc < 1 || napi_is_array(env, argv[0], &isarr) != napi_ok || !isarr) { napi_throw_type_error(env, nullptr, "bwtcDecompressMany(buffers, returnErrors)"); return nullptr; }
+    if (argc > 1) napi_get_value_bool(env, argv[1], &keep);
+    uint32_t count = 0;
+    napi_get_array_length(env, argv[0], &count);
+    std::vector<uint64_t> off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
+    std::vector<uint8_t*> ptr(count);
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value v; size_t len = 0;
+        napi_get_element(env, argv[0], i, &v);
+        if (!get_bytes(env, v, &ptr[i], &len)) { napi_throw_type_error(env, nullptr, "bwtcDecompressMany(buffers, ...): every input must be a Buffer or Uint8Array"); return nullptr; }
+        off[i + 1] = off[i] + len;
+    }
+    napi_value arr;
+    napi_create_array_with_length(env, count, &arr);
+    if (!count) return arr;
+    if (!ensure_ctx(env)) return nullptr;
+    const uint64_t total = off[count];
+    std::vector<uint8_t> flat((size_t)(total ? total : 1));
+    for (uint32_t i = 0; i < count; i++) if (off[i + 1] > off[i]) memcpy(flat.data() + off[i], ptr[i], (size_t)(off[i + 1] - off[i]));
+    std::vector<int32_t> status(count, 0);
+    int64_t n = p_bwtc_dec_batch(g_ctx, flat.data(), off.data(), count, nullptr, 0, out_off.data(), status.data(), nullptr);
+    std::vector<uint8_t> outb;
+    if (n == -21) {                                            // decoded; the sizes are known now
+        n = p_bwtc_lastsize(g_ctx);
+        outb.resize((size_t)(n > 0 ? n : 1));
+        n = p_bwtc_fetch(g_ctx, outb.data(), (uint64_t)n);
+    }
+    if (n < 0) return throw_code(env, n, "cjs_bwtc_decompress_batch");
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value b; void* dst;
+        if (status[i]) {
+            char text[96];
+            if (status[i] == -30) snprintf(text, sizeof text, "Bad magic");                        // lib/Util.js:150-152
+            else snprintf(text, sizeof text, "cjs_bwtc_decompress failed with code %d", (int)status[i]);
+            napi_value msg, idx;
+            napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
+            napi_create_error(env, nullptr, msg, &b);
+            napi_create_uint32(env, i, &idx);
+            napi_set_named_property(env, b, "index", idx);
+            if (!keep) { napi_throw(env, b); return nullptr; }
+        } else if (out_off[i + 1] > out_off[i]) napi_create_buffer_copy(env, (size_t)(out_off[i + 1] - out_off[i]), outb.data() + out_off[i], &dst, &b);
+        else napi_create_buffer(env, 0, &dst, &b);
+        napi_set_element(env, arr, i, b);
+    }
+    return arr;
+}
+
 // suffixsort(T, SA: Int32Array, n)                                = BWT.suffixsort
 static napi_value SuffixSort(napi_env env, napi_callback_info info) {
     size_t argc = 3; napi_value argv[3];
@@ -650,6 +706,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"suffixsort", nullptr, SuffixSort, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtcCompress", nullptr, BwtcCompress, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtcCompressMany", nullptr, BwtcCompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"bwtcDecompressMany", nullptr, BwtcDecompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"configure", nullptr, Configure, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_default, nullptr},
     };

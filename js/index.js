@@ -9,6 +9,7 @@
 //   Bzip2.decompressFile / decompressBlock / table   -> MI355X (GPU decoder K7-K9)
 //   Bzip2.decompressFiles(inputs, [multistream], [returnErrors]) -> MI355X, many independent inputs in one call (not in the reference)
 //   BWTC.decompressFile                               -> host range decoder + MI355X inverse BWT
+//   BWTC.decompressFiles(inputs, [returnErrors])      -> MI355X, many independent streams in one call (not in the reference)
 //   everything else (the other 12 codecs)
 //       -> delegated unchanged to an installed reference package (require('compressjs')), when
 //          there is one; otherwise those properties throw.
@@ -190,6 +191,15 @@ BWTC.decompressFile = function(inStream, outStream) {               // lib/BWTC.
   need();
   var bytes = inputBytes(inStream);
   return deliver(addon.bwtcDecompress(bytes), outStream);
+};
+// Not in the reference: many independent BWTC streams in one call - [BWTC.decompressFile(x) for every x] (cjs_bwtc_decompress_batch;
+// levels 6-9 run one range decoder per input on the GPU).  An input that fails throws what decompressFile throws for it, with
+// .index - or, with returnErrors, that error takes its place in the array and the others are still delivered.
+BWTC.decompressFiles = function(inputs, returnErrors) {
+  need();
+  var bufs = [];
+  for (var i = 0; i < inputs.length; i++) bufs.push(inputBytes(inputs[i]));
+  return addon.bwtcDecompressMany(bufs, !!returnErrors).map(function(b) { return b instanceof Error ? b : deliver(b, null); });
 };
 
 // Not in the reference (which is single-threaded JavaScript): which GPUs Bzip2.compressFile uses and how many bzip2
