@@ -21,6 +21,8 @@ using namespace cjs;
 
 extern "C" int cjs_dbg_bwtc_dec_batch_syncs(cjs_ctx* c) { return c ? c->bwtc_dec_batch_syncs : 0; }
 extern "C" int cjs_dbg_bwtc_dec_batch_fallbacks(cjs_ctx* c) { return c ? c->bwtc_dec_batch_fallbacks : 0; }
+static int g_k6_groups = 0;                                       // groups of the last run_groups (cjs_unbwt_linear_batch has no context)
+extern "C" int cjs_dbg_k6_groups(void) { return g_k6_groups; }
 
 namespace {
 
@@ -55,6 +57,7 @@ void cut_groups(std::vector<K6Blk>& rows, std::vector<size_t>& ends, size_t* ws_
 
 int run_groups(const std::vector<K6Blk>& rows, const std::vector<size_t>& ends, const K6Blk* d_rows, const u8* dT, u8* dU, void* ws, hipStream_t st) {
     size_t g0 = 0;
+    g_k6_groups = (int)ends.size();
     for (size_t e : ends) {
         u32 max_n = 0;
         for (size_t k = g0; k < e; k++) if (rows[k].n > max_n) max_n = rows[k].n;

@@ -33,7 +33,8 @@ int64_t cjs_bz2_compress_device(cjs_ctx* ctx, const void* d_in, uint64_t in_len,
  * cuts from that document (a document start starts a fresh block and a fresh run), its stream header (:903-906),
  * combined CRC (:917) and trailer (:925-927) are its own.  Documents are packed back to back: document d is input bytes
  * [off[d], off[d+1]), off = count + 1 nondecreasing offsets; empty documents are allowed (a 14-byte stream); one level for
- * the call.  Stream d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0, byte-aligned and back to back without padding -
+ * the call.  off[0] need not be 0: the bytes in front of it belong to no document (a run among them does not reach into
+ * document 0).  Stream d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0, byte-aligned and back to back without padding -
  * the whole output is also a valid multi-stream .bz2 file (cjs_bz2_decompress with multistream != 0 decodes it).
  * Both return the total number of bytes written (count == 0: 0), or CJS_E_LEVEL, CJS_E_ARG (null pointers, decreasing
  * offsets, d_out not 4-byte aligned, and - as in cjs_bz2_compress_device - a d_out of fewer than 64 bytes), CJS_E_NOSPACE
@@ -63,8 +64,9 @@ int cjs_bwtc_last_times(cjs_ctx* ctx, float* out5);
  * cjs_bwtc_compress(ctx, doc_d, len_d, level, ..., declared_size = len_d), i.e. to BWTC.compressFile(Buffer, null, level)
  * (lib/BWTC.js:12-139, lib/Util.js:105-142) on document d alone - its own magic, varint of len_d + 1 and coder start; its blocks
  * are the ceil(len_d / (level * 100000)) fixed-size pieces of that document (lib/BWTC.js:27), a document start starts a fresh block.
- * Documents are packed back to back: document d is input bytes [off[d], off[d+1]), off = count + 1 nondecreasing offsets; empty
- * documents are allowed and give the reference's stream for empty input.  One level for the call; a level outside 1..9 means 9
+ * Documents are packed back to back: document d is input bytes [off[d], off[d+1]), off = count + 1 nondecreasing offsets (off[0]
+ * need not be 0: the bytes in front of it belong to no document); empty documents are allowed and give the reference's stream for
+ * empty input.  One level for the call; a level outside 1..9 means 9
  * (lib/BWTC.js:16-19).  Stream d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0, back to back.
  * Both return the total number of bytes written (count == 0: 0), or CJS_E_ARG (null pointers, decreasing offsets), CJS_E_NOSPACE
  * (out_cap too small: out_off is written all the same; cjs_bwtc_compress_batch_bound = total_len + total_len / 4 + 4096 * count,
@@ -166,7 +168,8 @@ int32_t cjs_suffixsort(const uint8_t* T, int32_t* SA, uint32_t n);
 /* = BWT.unbwtransform(T, U, LF, n, pidx)                (reference: lib/BWT.js:352-363); list ranking */
 int32_t cjs_unbwt_linear(const uint8_t* T, uint8_t* U, uint32_t n, uint32_t pidx);
 /* The same for `count` blocks in one call (host pointers): block k = T[off[k] .. off[k+1]) with primary index pidx[k], its text
- * to U[off[k] .. off[k+1]); every block is what cjs_unbwt_linear gives for it alone.  One sequence of launches per group of
+ * to U[off[k] .. off[k+1]) (off[0] need not be 0; nothing in front of U[off[0]] is written); every block is what cjs_unbwt_linear
+ * gives for it alone.  One sequence of launches per group of
  * blocks (the list-ranking workspace of a group, ~20 bytes per byte, stays inside 512 MiB), no host wait in between; a (T, pidx)
  * pair that is no BWT gets the reference's literal walk.  CJS_E_ARG: pidx[k] > its block's length, decreasing offsets. */
 int32_t cjs_unbwt_linear_batch(const uint8_t* T, const uint64_t* off, const uint32_t* pidx, uint32_t count, uint8_t* U);
@@ -243,8 +246,9 @@ float cjs_bz2_last_decode_ms(cjs_ctx* ctx);
  * as its neighbour's bytes - either the decoded bytes or the reference's Err code in status[d] (0, or -2 / -5 / -7 as above; which
  * one, and when, follows the reference's sequential order inside the document: a bad block CRC in block 1 wins over a structural
  * error behind block 2).  detail[3d .. 3d+2] = optDetail number, CRC got, CRC expected, as cjs_bz2_last_detail reports them
- * (`detail` may be NULL).  Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, any byte alignment, empty
- * documents allowed (status -2, detail 1).  Results lie back to back: result d is out[out_off[d] .. out_off[d+1]), out_off[0] = 0;
+ * (`detail` may be NULL).  Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, any byte alignment (off[0]
+ * need not be 0), empty documents allowed (status -2, detail 1).  Results lie back to back: result d is
+ * out[out_off[d] .. out_off[d+1]), out_off[0] = 0;
  * a failed document contributes no bytes and changes nothing for any other document.
  * Both return the total number of decoded bytes (>= 0 even when documents failed; count == 0: 0).  Negative returns are call-level
  * only: CJS_E_ARG (null ctx / off / out_off / status, decreasing offsets, null `in` with a non-empty batch), CJS_E_NOGPU,
@@ -274,8 +278,9 @@ int64_t cjs_bwtc_fetch(cjs_ctx* ctx, uint8_t* out, uint64_t out_cap);
  * either the decoded bytes (status[d] = 0), or status[d] = -30 (bad magic) / -31 (corrupt or truncated) and no bytes.  A damaged
  * stream that the single call decodes without error into other bytes comes out as those same bytes.  declared[d] (may be NULL)
  * is the size recorded in the header where the single call reports it, else -1 (unknown; also: bad magic, a size cut short).
- * Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, at any byte alignment; empty documents are allowed
- * (-30).  A read behind a document's end is end-of-input for that document, never its neighbour's bytes.  Result d is
+ * Document d is in[off[d] .. off[d+1]), off = count + 1 nondecreasing offsets, at any byte alignment (off[0] need not be 0); empty
+ * documents are allowed (-30).  A read behind a document's end is end-of-input for that document, never its neighbour's bytes.
+ * Result d is
  * out[out_off[d] .. out_off[d+1]), out_off[0] = 0, back to back; a failed document contributes nothing and changes nothing for
  * any other.  Both forms return the total of decoded bytes (>= 0 also when documents failed; count == 0: 0).  Negative returns
  * are call-level only: CJS_E_ARG (null ctx / off / out_off / status, decreasing offsets, null `in` with bytes to read),
@@ -297,6 +302,7 @@ int64_t cjs_bwtc_decompress_batch_device(cjs_ctx* ctx, const void* d_in, const u
                                          uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared);
 int cjs_dbg_bwtc_dec_batch_syncs(cjs_ctx* ctx);      /* host<->device waits the last such call on ctx made itself */
 int cjs_dbg_bwtc_dec_batch_fallbacks(cjs_ctx* ctx);  /* documents of the last such call that took the host path */
+int cjs_dbg_k6_groups(void);          /* groups of blocks the last batched inverse BWT of the process ran (cjs_unbwt_linear_batch, cjs_bwtc_decompress_batch*): a new group after 65 535 blocks or 512 MiB of list-ranking workspace */
 
 /* Workload helper (not a compression entry point): bytes [first, first + n) of LCG(N, seed) - SURVEY.md 8(c), BASELINE.json
  * configs[3] "random printable ASCII" - written straight into HBM, so that every GPU of a multi-GPU run fills its own slice. */
