@@ -20,19 +20,19 @@
 #define SQRTPI 0x177245385090ull
 
 struct DecState {
-    u32 slots;
-    u8* d_in; size_t in_cap;
-    u64* d_cand; u32 cand_cap; u32* d_ncand;
-    void* slab;                      // per-slot arrays
-    DecBuf D;
-    u64* d_bcand; u32* d_slotOf; u64* d_outOff; u32* d_crcOut;
-    u8* d_out; size_t out_cap; u64 out_size;
-    int detail; u32 crc_got, crc_want;
+    u32 slots = 0;
+    u8* d_in = nullptr; size_t in_cap = 0;
+    u64* d_cand = nullptr; size_t cand_cap = 0; u32* d_ncand = nullptr;      // (cand_cap, dcand_cap: candidates, not bytes)
+    void* slab = nullptr;            // per-slot arrays
+    DecBuf D = {};
+    u64* d_bcand = nullptr; u32* d_slotOf = nullptr; u64* d_outOff = nullptr; u32* d_crcOut = nullptr;
+    u8* d_out = nullptr; size_t out_cap = 0; u64 out_size = 0;
+    int detail = 0; u32 crc_got = 0, crc_want = 0;
     std::vector<u64> tab_pos, tab_size;
     // a batch of documents (dec_batch): grow-only
     u8* d_raw = nullptr; size_t raw_cap = 0;          // the host form's packed documents
     void* d_meta = nullptr; size_t meta_cap = 0;      // bases, offsets, heads, chunk -> document, outcome records
-    DecCand* d_dcand = nullptr; u32 dcand_cap = 0;
+    DecCand* d_dcand = nullptr; size_t dcand_cap = 0;
     u32* d_blim = nullptr;                            // [slots] limit chunk of the candidates of a k7_decode launch (in the slab)
 };
 
@@ -45,6 +45,17 @@ static hipError_t dec_sync(hipStream_t st) { g_dec_syncs++; return hipStreamSync
 #define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return CJS_E_HIP - (int)e_; } while (0)
 
 static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// a grow-only device array of `elem`-byte items with room for `need` of them: a quarter more with `slack`, else exactly `need`
+// (d_in and the candidate arrays, which are sized by the input alone)
+static int grow_dev(void** p, size_t* have, size_t need, size_t elem = 1, bool slack = true) {
+    if (need <= *have) return CJS_OK;
+    (void)hipFree(*p); *p = nullptr; *have = 0;
+    if (slack) need += need / 4;
+    TRYH(hipMalloc(p, need * elem));
+    *have = need;
+    return CJS_OK;
+}
 
 static int dec_alloc(DecState& S, u32 slots) {
     if (S.slab) { (void)hipFree(S.slab); S.slab = nullptr; }
@@ -133,14 +144,18 @@ void dec_free(DecState* S) {
     delete S;
 }
 
-static int dec_get(DecState** ps, u32 slots) {
-    if (*ps) return CJS_OK;
-    DecState* S = new DecState();
-    S->slots = 0; S->d_in = nullptr; S->in_cap = 0; S->d_cand = nullptr; S->cand_cap = 0; S->d_ncand = nullptr;
-    S->slab = nullptr; S->d_out = nullptr; S->out_cap = 0; S->out_size = 0; S->detail = 0; S->crc_got = S->crc_want = 0;
-    const int rc = dec_alloc(*S, slots);
-    if (rc) { dec_free(S); return rc; }
-    *ps = S;
+// every decode call starts here: the state, made on first use, with the last call's outcome cleared
+static int dec_begin(DecState** ps, u32 slots) {
+    if (!*ps) {
+        DecState* S = new DecState();
+        const int rc = dec_alloc(*S, slots);
+        if (rc) { dec_free(S); return rc; }
+        *ps = S;
+    }
+    DecState& S = **ps;
+    g_dec_syncs = 0;
+    S.out_size = 0; S.detail = 0; S.crc_got = S.crc_want = 0;
+    S.tab_pos.clear(); S.tab_size.clear();
     return CJS_OK;
 }
 
@@ -164,19 +179,13 @@ static int ensure_out(DecState& S, u64 need, hipStream_t st) {
 // the stream, padded with zeros (bits past EOF read as 0, lib/BitStream.js:84), resident in HBM
 static int stage_input(DecState& S, const u8* in, u64 len, bool in_dev, hipStream_t st) {
     const size_t need = ((len + 255) & ~(size_t)255) + 1024;
-    if (need > S.in_cap) {
-        (void)hipFree(S.d_in); S.d_in = nullptr; S.in_cap = 0;
-        TRYH(hipMalloc((void**)&S.d_in, need));
-        S.in_cap = need;
-    }
+    int rc = grow_dev((void**)&S.d_in, &S.in_cap, need, 1, false);
+    if (rc) return rc;
     TRYH(hipMemsetAsync(S.d_in + (len & ~(u64)255), 0, need - (len & ~(u64)255), st));
     if (len) TRYH(hipMemcpyAsync(S.d_in, in, len, in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    const u32 ccap = (u32)std::min<u64>(len / 4 + 16, 1u << 27);      // a 48-bit pattern cannot occur more often than every 6 bytes
-    if (ccap > S.cand_cap) {
-        (void)hipFree(S.d_cand); S.d_cand = nullptr; S.cand_cap = 0;
-        TRYH(hipMalloc((void**)&S.d_cand, (size_t)ccap * 8));
-        S.cand_cap = ccap;
-    }
+    // a 48-bit pattern cannot occur more often than every 6 bytes
+    rc = grow_dev((void**)&S.d_cand, &S.cand_cap, (size_t)std::min<u64>(len / 4 + 16, 1u << 27), 8, false);
+    if (rc) return rc;
     S.D.in32 = (const u32*)S.d_in;
     S.D.zeroChunk = ((len + 255) >> 8) + 1;          // [zeroChunk*256, +256) is inside the 1024 zero bytes
     S.D.candLim = nullptr;                           // one stream: every block reads zeros from zeroChunk on
@@ -210,7 +219,6 @@ struct Walker {
         }
         return v;
     }
-    bool eof(u64 p) const { return ((p + 7) >> 3) >= len; }          // lib/Util.js:30 on the coerced buffer stream
 };
 
 static int fail(DecState& S, int code, int detail, u32 got = 0, u32 want = 0) {
@@ -218,15 +226,18 @@ static int fail(DecState& S, int code, int detail, u32 got = 0, u32 want = 0) {
     return code;
 }
 
-// reads the 4-byte stream header at byte `base` (lib/Bzip2.js:137-152); 0 or an error
-static int read_header(DecState& S, Walker& W, u64 base, u32* dbufSize) {
-    if (W.len < base + 4) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_BAD_MAGIC);
-    const u64 h = W.rd(base * 8, 32);
-    if ((h >> 8) != 0x425a68u) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_BAD_MAGIC);
+// the 4-byte stream header `h` (lib/Bzip2.js:137-152); have: the document holds all 4 bytes.  0 or an error
+static int check_header(DecState& S, bool have, u32 h, u32* dbufSize) {
+    if (!have || (h >> 8) != 0x425a68u) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_BAD_MAGIC);
     const int level = (int)(h & 0xffu) - '0';
     if (level < 1 || level > 9) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_LEVEL);
     *dbufSize = 100000u * (u32)level;
     return 0;
+}
+// the same on the 4 bytes at byte `base` of the single stream, fetched only when it holds them
+static int read_header(DecState& S, Walker& W, u64 base, u32* dbufSize) {
+    const bool have = W.len >= base + 4;
+    return check_header(S, have, have ? (u32)W.rd(base * 8, 32) : 0, dbufSize);
 }
 
 // the reference's per-block checks, in its order, on a k7_decode result
@@ -238,11 +249,15 @@ static int block_error(DecState& S, const DecResult& r, u32 dbufSize) {
     return 0;
 }
 
-struct ValidBlk { u32 slot; u64 pos; u32 crc; };
+struct ValidBlk { u32 slot, crc; u64 pos; };       // a block on the chain: its slot, its stored CRC, its bit position
 
-// K8 + K9 of the chain blocks of one batch; appends to S.d_out.  Returns 0 or an error.
-static int process_valid(DecState& S, hipStream_t st, std::vector<ValidBlk>& valid, const std::vector<DecResult>& res) {
+// K8 + K9 of the chain blocks of one slot batch: their bytes go to S.d_out from S.out_size on, in the order of `valid`.  Gives
+// per block its decoded size, the CRC of its bytes and its offset in S.d_out, and decides nothing: S.out_size, the table and
+// what a CRC that differs means are the caller's.  Returns 0 or an error.
+static int run_k8k9(DecState& S, hipStream_t st, const std::vector<ValidBlk>& valid, std::vector<u32>& size, std::vector<u32>& crc,
+                    std::vector<u64>& outOff) {
     const u32 nv = (u32)valid.size();
+    size.resize(nv); crc.resize(nv); outOff.resize(nv);
     if (!nv) return 0;
     std::vector<u32> slotOf(nv);
     for (u32 k = 0; k < nv; k++) slotOf[k] = valid[k].slot;
@@ -254,26 +269,31 @@ static int process_valid(DecState& S, hipStream_t st, std::vector<ValidBlk>& val
     std::vector<u32> blkOut(S.slots);
     TRYH(hipMemcpyAsync(blkOut.data(), S.D.blkOut, S.slots * 4, hipMemcpyDeviceToHost, st));
     TRYH(dec_sync(st));
-    std::vector<u64> outOff(nv);
     u64 o = S.out_size;
-    for (u32 k = 0; k < nv; k++) { outOff[k] = o; o += blkOut[valid[k].slot]; }
+    for (u32 k = 0; k < nv; k++) { size[k] = blkOut[valid[k].slot]; outOff[k] = o; o += size[k]; }
     rc = ensure_out(S, o + 64, st);
     if (rc) return rc;
     S.D.out = S.d_out;
     TRYH(hipMemcpyAsync(S.d_outOff, outOff.data(), nv * 8, hipMemcpyHostToDevice, st));
     rc = k9_expand(S.D, nv, st);
     if (rc) return rc;
-    std::vector<u32> crc(nv);
     TRYH(hipMemcpyAsync(crc.data(), S.d_crcOut, nv * 4, hipMemcpyDeviceToHost, st));
     TRYH(dec_sync(st));
-    for (u32 k = 0; k < nv; k++) {
-        // the reference has written the block before it compares the CRC (:437-445)
-        S.out_size = outOff[k] + blkOut[valid[k].slot];
+    return 0;
+}
+
+// the single stream's K8/K9 step: the blocks in the reference's order, up to the first whose CRC differs
+static int append_blocks(DecState& S, hipStream_t st, std::vector<ValidBlk>& valid) {
+    std::vector<u32> size, crc;
+    std::vector<u64> outOff;
+    const int rc = run_k8k9(S, st, valid, size, crc, outOff);
+    if (rc) return rc;
+    for (size_t k = 0; k < valid.size(); k++) {
+        S.out_size += size[k];                     // the reference has written the block before it compares the CRC (:437-445)
         if (crc[k] != valid[k].crc) return fail(S, DEC_DATA_ERROR, DEC_DETAIL_BLOCK_CRC, crc[k], valid[k].crc);
         S.tab_pos.push_back(valid[k].pos);
-        S.tab_size.push_back(blkOut[valid[k].slot]);
+        S.tab_size.push_back(size[k]);
     }
-    (void)res;
     valid.clear();
     return 0;
 }
@@ -305,22 +325,95 @@ static int decode_batch(DecState& S, hipStream_t st, const u64* pos, u32 count, 
     return 0;
 }
 
+// the block candidates of a call, and the slot batch of them that k7_decode decoded last
+struct Slots {
+    std::vector<u64> bpos;               // bit positions of the block magics, ascending
+    std::vector<u32> blim;               // (a batch of documents) their limit chunks
+    std::vector<DecResult> res;          // of candidates [first, first + count)
+    u32 first = 0, count = 0;
+};
+static int decode_from(DecState& S, hipStream_t st, Slots& w, u32 need) {
+    w.first = need;
+    w.count = (u32)std::min<size_t>(S.slots, w.bpos.size() - need);
+    return decode_batch(S, st, w.bpos.data() + need, w.count, w.res, w.blim.empty() ? nullptr : w.blim.data() + need);
+}
+
+// Where a walk finds its document's candidates and the words behind an end-of-stream magic.  A source has B and len - the
+// document's first bit among the candidates' positions and its length in bytes -, find(bit): -1 when no magic starts at that bit,
+// else whether it is the end-of-stream one - and for the end magic found last stream_crc(p) and header(base): the 32 bits behind
+// it and the 4 bytes at the next byte boundary.
+static u64 cand_key(u64 c) { return c; }
+static u64 cand_key(const DecCand& c) { return c.key; }
+template <class C> static const C* cand_at(const std::vector<C>& cand, u64 bit) {       // cand: ascending by key = (bit << 1) | end
+    const auto it = std::lower_bound(cand.begin(), cand.end(), bit << 1, [](const C& x, u64 k) { return cand_key(x) < k; });
+    return it != cand.end() && (cand_key(*it) >> 1) == bit ? &*it : nullptr;
+}
+// The single stream reads the words where the chain meets an end magic (Walker::rd: a copy and a wait each in the device form;
+// fetched for every candidate, a stream stuffed with fake end magics would pay for all of them).
+struct StreamSrc {
+    Walker& W; const std::vector<u64>& cand; u64 B, len;
+    int find(u64 bit) const { const u64* at = cand_at(cand, bit); return at ? (int)(*at & 1u) : -1; }
+    u32 stream_crc(u64 p) { return (u32)W.rd(p + 48, 32); }
+    u32 header(u64 base) { return (u32)W.rd(base * 8, 32); }
+};
+// A document of a batch has them in the candidate's record (k7_scan_docs); cand: of the whole batch.
+struct BatchSrc {
+    const std::vector<DecCand>& cand; u64 B, len; const DecCand* at;
+    int find(u64 bit) { at = cand_at(cand, bit); return at ? (int)(at->key & 1u) : -1; }
+    u32 stream_crc(u64) const { return at->a; }
+    u32 header(u64) const { return at->b; }
+};
+
+struct Chain { u64 p; u32 dbufSize, streamCRC; };      // a walk in progress: bit position in the document, the stream's dbufSize and CRC so far
+
+// One document's chain from c.p on, in the reference's order: block, block, ..., end-of-stream magic, stream CRC, and with
+// `multistream` the next stream's header and so on.  The blocks on the chain are appended to `valid`.  Returns 0 when the
+// document is finished, an Err code when it fails (through fail()), 1 when the next block - candidate *need - is outside the
+// decoded slot batch.
+template <class Src>
+static int walk_chain(DecState& S, Src& src, Chain& c, int multistream, bool check_stream_crc, const Slots& w,
+                      std::vector<ValidBlk>& valid, u32* need) {
+    const auto eof = [&src](u64 q) { return ((q + 7) >> 3) >= src.len; };        // lib/Util.js:30 on the coerced buffer stream
+    while (!eof(c.p)) {                                                          // :462
+        const int end = src.find(src.B + c.p);
+        if (end < 0) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_NONE);              // :160-161
+        if (end) {                                                               // end of stream :157-159,:465-477
+            const u32 target = src.stream_crc(c.p);
+            if (check_stream_crc && target != c.streamCRC) return fail(S, DEC_DATA_ERROR, DEC_DETAIL_STREAM_CRC, c.streamCRC, target);
+            if (!multistream || eof(c.p + 80)) return 0;
+            const u64 base = (c.p + 80 + 7) >> 3;
+            const bool have = src.len >= base + 4;
+            const int rc = check_header(S, have, have ? src.header(base) : 0, &c.dbufSize);
+            if (rc) return rc;
+            c.p = (base + 4) * 8;
+            c.streamCRC = 0;
+            continue;
+        }
+        const u32 idx = (u32)(std::lower_bound(w.bpos.begin(), w.bpos.end(), src.B + c.p) - w.bpos.begin());
+        if (idx < w.first || idx >= w.first + w.count) { *need = idx; return 1; }
+        const DecResult& r = w.res[idx - w.first];
+        c.streamCRC = r.crc ^ ((c.streamCRC << 1) | (c.streamCRC >> 31));        // :163-164
+        const int rc = block_error(S, r, c.dbufSize);
+        if (rc) return rc;
+        valid.push_back({idx - w.first, r.crc, src.B + c.p});
+        c.p = r.endbit - src.B;
+    }
+    return 0;
+}
+
 int64_t dec_stream(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 len, bool in_dev, int multistream,
                    bool check_stream_crc) {
-    int rc = dec_get(ps, slots);
+    int rc = dec_begin(ps, slots);
     if (rc) return rc;
     DecState& S = **ps;
-    g_dec_syncs = 0;
-    S.out_size = 0; S.detail = 0; S.crc_got = S.crc_want = 0;
-    S.tab_pos.clear(); S.tab_size.clear();
     Walker W = {S, st, in_dev ? nullptr : in, len, 0};
     rc = stage_input(S, in, len, in_dev, st);
     if (rc) return rc;
-    u32 dbufSize = 0;
-    rc = read_header(S, W, 0, &dbufSize);                                        // :137-152, before anything else
+    Chain c = {32, 0, 0};
+    rc = read_header(S, W, 0, &c.dbufSize);                                      // :137-152, before anything else
     if (rc) return rc;
     // candidates
-    rc = k7_scan(S.d_in, len, 32, S.d_cand, S.d_ncand, S.cand_cap, st);
+    rc = k7_scan(S.d_in, len, 32, S.d_cand, S.d_ncand, (u32)S.cand_cap, st);
     if (rc) return rc;
     u32 nc = 0;
     TRYH(hipMemcpyAsync(&nc, S.d_ncand, 4, hipMemcpyDeviceToHost, st));
@@ -329,68 +422,33 @@ int64_t dec_stream(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 l
     std::vector<u64> cand(nc);
     if (nc) { g_dec_syncs++; TRYH(hipMemcpy(cand.data(), S.d_cand, (size_t)nc * 8, hipMemcpyDeviceToHost)); }
     std::sort(cand.begin(), cand.end());
-    std::vector<u64> bpos;                                                       // block-magic positions only
-    for (u64 c : cand) if (!(c & 1u)) bpos.push_back(c >> 1);
-    rc = dec_fit_slots(S, slots, bpos.size());
+    Slots w;
+    for (u64 x : cand) if (!(x & 1u)) w.bpos.push_back(x >> 1);
+    rc = dec_fit_slots(S, slots, w.bpos.size());
     if (rc) return rc;
 
-    std::vector<DecResult> res;
+    StreamSrc src = {W, cand, 0, len};
     std::vector<ValidBlk> valid;
-    u32 bfirst = 0, bcount = 0;
-    u64 p = 32;
-    u32 streamCRC = 0;
     for (;;) {
-        int term = 0;          // 0: stream finished, <0: error, 1: need a batch starting at `need`
         u32 need = 0;
-        for (;;) {
-            if (W.eof(p)) break;                                                 // :462
-            const u64 key = p << 1;
-            auto it = std::lower_bound(cand.begin(), cand.end(), key);
-            if (it == cand.end() || (*it >> 1) != p) { term = fail(S, DEC_NOT_BZIP, DEC_DETAIL_NONE); break; }     // :160-161
-            if (*it & 1u) {                                                      // end of stream :157-159,:465-477
-                const u32 target = (u32)W.rd(p + 48, 32);
-                if (check_stream_crc && target != streamCRC) { term = fail(S, DEC_DATA_ERROR, DEC_DETAIL_STREAM_CRC, streamCRC, target); break; }
-                if (multistream && !W.eof(p + 80)) {
-                    const u64 base = (p + 80 + 7) >> 3;
-                    term = read_header(S, W, base, &dbufSize);
-                    if (term) break;
-                    p = (base + 4) * 8;
-                    streamCRC = 0;
-                    continue;
-                }
-                break;
-            }
-            const u32 idx = (u32)(std::lower_bound(bpos.begin(), bpos.end(), p) - bpos.begin());
-            if (idx < bfirst || idx >= bfirst + bcount) { term = 1; need = idx; break; }
-            const DecResult& r = res[idx - bfirst];
-            streamCRC = r.crc ^ ((streamCRC << 1) | (streamCRC >> 31));          // :163-164
-            term = block_error(S, r, dbufSize);
-            if (term) break;
-            valid.push_back({idx - bfirst, p, r.crc});
-            p = r.endbit;
-        }
+        const int term = walk_chain(S, src, c, multistream, check_stream_crc, w, valid, &need);
         if (W.rd_err) return W.rd_err;
-        const int saved_detail = S.detail; const u32 sg = S.crc_got, sw = S.crc_want;
-        rc = process_valid(S, st, valid, res);                                   // earlier blocks' CRC errors come first
+        // A CRC error of the blocks in front of the point where the walk stopped comes first.  Without one the walk's own error
+        // stands as it is: the step writes S.detail and the CRC pair only through that fail().
+        rc = append_blocks(S, st, valid);
         if (rc) return rc;
-        if (term < 0) { S.detail = saved_detail; S.crc_got = sg; S.crc_want = sw; return term; }
-        if (term == 0) break;
-        bfirst = need;
-        bcount = (u32)std::min<size_t>(S.slots, bpos.size() - need);
-        rc = decode_batch(S, st, bpos.data() + bfirst, bcount, res);
+        if (term < 0) return term;
+        if (term == 0) return (int64_t)S.out_size;
+        rc = decode_from(S, st, w, need);
         if (rc) return rc;
     }
-    return (int64_t)S.out_size;
 }
 
 // Bunzip.decodeBlock (lib/Bzip2.js:482-503)
 int64_t dec_block(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 len, u64 bitpos) {
-    int rc = dec_get(ps, slots);
+    int rc = dec_begin(ps, slots);
     if (rc) return rc;
     DecState& S = **ps;
-    g_dec_syncs = 0;
-    S.out_size = 0; S.detail = 0; S.crc_got = S.crc_want = 0;
-    S.tab_pos.clear(); S.tab_size.clear();
     Walker W = {S, st, in, len, 0};
     u32 dbufSize = 0;
     rc = read_header(S, W, 0, &dbufSize);
@@ -405,93 +463,51 @@ int64_t dec_block(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 le
     if (rc) return rc;
     rc = block_error(S, res[0], dbufSize);
     if (rc) return rc;
-    std::vector<ValidBlk> valid;
-    valid.push_back({0, bitpos, res[0].crc});
-    rc = process_valid(S, st, valid, res);
+    std::vector<ValidBlk> valid = {{0, res[0].crc, bitpos}};
+    rc = append_blocks(S, st, valid);
     if (rc) return rc;
     return (int64_t)S.out_size;
 }
 
 // ---------------------------------------------------------------------------------------------
 // A batch of documents (cjs_bz2_decompress_batch): document d decodes as Bzip2.decompressFile (lib/Bzip2.js:454-481) does on it
-// alone.  One staging pass, one scan and shared slot batches for all of them (k7_docs.hip); the chain walk below is dec_stream's,
-// run per document - header, blocks, end magic, stream CRC, next stream if `multistream` - against the document's base and
-// length, over the sorted candidates of the whole batch.  Everything it reads - headers, stream CRCs, follow-on headers - came
-// to the host in bulk with the candidates.
+// alone.  One staging pass, one scan and shared slot batches for all of them (k7_docs.hip).  The chain walk is walk_chain, the one
+// dec_stream runs, once per document against the document's base and length, over the sorted candidates of the whole batch; only
+// its source differs (BatchSrc): everything the walk reads - headers, stream CRCs, follow-on headers - came to the host in bulk
+// with the candidates.
 // ---------------------------------------------------------------------------------------------
 struct DocOut { int status; u32 detail, got, want; u64 src, size; bool crc_bad; };
-struct ValidDoc { u32 slot, crc, doc; };
-
-static int grow_dev(void** p, size_t* have, size_t need) {
-    if (need <= *have) return CJS_OK;
-    (void)hipFree(*p); *p = nullptr; *have = 0;
-    need += need / 4;
-    TRYH(hipMalloc(p, need));
-    *have = need;
-    return CJS_OK;
-}
 
 static void doc_fail(DecState& S, DocOut& o, int code) { o.status = code; o.detail = (u32)S.detail; o.got = S.crc_got; o.want = S.crc_want; }
 
-// the 4-byte stream header `h` (lib/Bzip2.js:137-152); have: the document holds all 4 bytes
-static int check_header(DecState& S, bool have, u32 h, u32* dbufSize) {
-    if (!have || (h >> 8) != 0x425a68u) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_BAD_MAGIC);
-    const int level = (int)(h & 0xffu) - '0';
-    if (level < 1 || level > 9) return fail(S, DEC_NOT_BZIP, DEC_DETAIL_LEVEL);
-    *dbufSize = 100000u * (u32)level;
-    return 0;
-}
-
-// K8 + K9 of the chain blocks of one slot batch, whatever documents they belong to (`valid` is in document order, so the decoded
-// bytes of a document are contiguous); a block whose CRC differs fails its document unless an earlier block already has: the
-// reference meets block CRCs in stream order, and every block listed here lies in front of the point where the walk stopped.
-static int process_valid_docs(DecState& S, hipStream_t st, std::vector<ValidDoc>& valid, std::vector<DocOut>& R) {
-    const u32 nv = (u32)valid.size();
-    if (!nv) return 0;
-    std::vector<u32> slotOf(nv);
-    for (u32 k = 0; k < nv; k++) slotOf[k] = valid[k].slot;
-    TRYH(hipMemcpyAsync(S.d_slotOf, slotOf.data(), nv * 4, hipMemcpyHostToDevice, st));
-    int rc = k8_run(S.D, nv, st);
+// The batch's K8/K9 step: the chain blocks of one slot batch, whatever documents they belong to (vdoc[k]: the document of
+// valid[k]; `valid` is in document order, so the decoded bytes of a document are contiguous).  A block whose CRC differs fails its
+// document unless an earlier block already has: the reference meets block CRCs in stream order, and every block listed here lies
+// in front of the point where the walk stopped.
+static int append_docs(DecState& S, hipStream_t st, std::vector<ValidBlk>& valid, std::vector<u32>& vdoc, std::vector<DocOut>& R) {
+    std::vector<u32> size, crc;
+    std::vector<u64> outOff;
+    const int rc = run_k8k9(S, st, valid, size, crc, outOff);
     if (rc) return rc;
-    rc = k9_sizes(S.D, nv, st);
-    if (rc) return rc;
-    std::vector<u32> blkOut(S.slots);
-    TRYH(hipMemcpyAsync(blkOut.data(), S.D.blkOut, S.slots * 4, hipMemcpyDeviceToHost, st));
-    TRYH(dec_sync(st));
-    std::vector<u64> outOff(nv);
-    u64 o = S.out_size;
-    for (u32 k = 0; k < nv; k++) { outOff[k] = o; o += blkOut[valid[k].slot]; }
-    rc = ensure_out(S, o + 64, st);
-    if (rc) return rc;
-    S.D.out = S.d_out;
-    TRYH(hipMemcpyAsync(S.d_outOff, outOff.data(), nv * 8, hipMemcpyHostToDevice, st));
-    rc = k9_expand(S.D, nv, st);
-    if (rc) return rc;
-    std::vector<u32> crc(nv);
-    TRYH(hipMemcpyAsync(crc.data(), S.d_crcOut, nv * 4, hipMemcpyDeviceToHost, st));
-    TRYH(dec_sync(st));
-    for (u32 k = 0; k < nv; k++) {
-        DocOut& d = R[valid[k].doc];
+    for (size_t k = 0; k < valid.size(); k++) {
+        DocOut& d = R[vdoc[k]];
         if (!d.size) d.src = outOff[k];
-        d.size += blkOut[valid[k].slot];
+        d.size += size[k];
+        S.out_size += size[k];
         if (crc[k] != valid[k].crc && !d.crc_bad) {
             d.crc_bad = true;
             d.status = DEC_DATA_ERROR; d.detail = DEC_DETAIL_BLOCK_CRC; d.got = crc[k]; d.want = valid[k].crc;
         }
     }
-    S.out_size = o;
-    valid.clear();
+    valid.clear(); vdoc.clear();
     return 0;
 }
 
 int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const u64* off, u32 count, bool dev, int multistream,
                   u64* out_off, int* status, u32* detail) {
-    int rc = dec_get(ps, slots);
+    int rc = dec_begin(ps, slots);
     if (rc) return rc;
     DecState& S = **ps;
-    g_dec_syncs = 0;
-    S.out_size = 0; S.detail = 0; S.crc_got = S.crc_want = 0;
-    S.tab_pos.clear(); S.tab_size.clear();
     // the offsets on the host; the staged layout
     std::vector<u64> offh((size_t)count + 1);
     if (dev) {
@@ -530,26 +546,16 @@ int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const 
         d_off = (const u64*)(M + o_off);
         d_src = S.d_raw;
     }
-    {
-        const size_t need = (size_t)staged + 1024;
-        if (need > S.in_cap) {
-            (void)hipFree(S.d_in); S.d_in = nullptr; S.in_cap = 0;
-            TRYH(hipMalloc((void**)&S.d_in, need));
-            S.in_cap = need;
-        }
-        TRYH(hipMemsetAsync(S.d_in + staged, 0, 1024, st));
-        const u32 ccap = (u32)std::min<u64>(staged / 4 + 16, 1u << 27);
-        if (ccap > S.dcand_cap) {
-            (void)hipFree(S.d_dcand); S.d_dcand = nullptr; S.dcand_cap = 0;
-            TRYH(hipMalloc((void**)&S.d_dcand, (size_t)ccap * sizeof(DecCand)));
-            S.dcand_cap = ccap;
-        }
-        S.D.in32 = (const u32*)S.d_in;
-        S.D.zeroChunk = (staged >> 8) + 1;          // inside the 1024 zero bytes behind the last document
-    }
+    rc = grow_dev((void**)&S.d_in, &S.in_cap, (size_t)staged + 1024, 1, false);
+    if (rc) return rc;
+    TRYH(hipMemsetAsync(S.d_in + staged, 0, 1024, st));
+    rc = grow_dev((void**)&S.d_dcand, &S.dcand_cap, (size_t)std::min<u64>(staged / 4 + 16, 1u << 27), sizeof(DecCand), false);
+    if (rc) return rc;
+    S.D.in32 = (const u32*)S.d_in;
+    S.D.zeroChunk = (staged >> 8) + 1;              // inside the 1024 zero bytes behind the last document
     rc = k7_stage(d_src, d_off, d_base, count, staged, S.d_in, d_cdoc, d_head, st);
     if (rc) return rc;
-    rc = k7_scan_batch(S.d_in, staged, d_off, d_base, d_cdoc, S.d_dcand, S.d_ncand, S.dcand_cap, st);
+    rc = k7_scan_batch(S.d_in, staged, d_off, d_base, d_cdoc, S.d_dcand, S.d_ncand, (u32)S.dcand_cap, st);
     if (rc) return rc;
     std::vector<u32> head(count);
     u32 nc = 0;
@@ -563,70 +569,40 @@ int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const 
         TRYH(dec_sync(st));
     }
     std::sort(cand.begin(), cand.end(), [](const DecCand& x, const DecCand& y) { return x.key < y.key; });
-    std::vector<u64> bpos;                                                       // block-magic positions only, and their limit chunks
-    std::vector<u32> blim;
-    for (const DecCand& c : cand) if (!(c.key & 1u)) { bpos.push_back(c.key >> 1); blim.push_back(c.a); }
-    rc = dec_fit_slots(S, slots, bpos.size());
+    Slots w;
+    for (const DecCand& x : cand) if (!(x.key & 1u)) { w.bpos.push_back(x.key >> 1); w.blim.push_back(x.a); }
+    rc = dec_fit_slots(S, slots, w.bpos.size());
     if (rc) return rc;
     S.D.candLim = S.d_blim;
 
     std::vector<DocOut> R(count, DocOut{0, 0, 0, 0, 0, 0, false});
-    std::vector<DecResult> res;
-    std::vector<ValidDoc> valid;
-    u32 bfirst = 0, bcount = 0;
+    std::vector<ValidBlk> valid;
+    std::vector<u32> vdoc;         // the document of valid[k]
     u32 d = 0;
     bool fresh = true;             // document d has not been started
-    u64 p = 0;                     // bit position in document d
-    u32 dbufSize = 0, streamCRC = 0;
+    Chain c = {0, 0, 0};
     for (;;) {
-        bool need_batch = false;
         u32 need = 0;
         while (d < count) {
-            const u64 B = base[d] * 8, len = offh[d + 1] - offh[d];
-            const auto eof = [len](u64 q) { return ((q + 7) >> 3) >= len; };     // lib/Util.js:30 on the coerced buffer stream
-            int term = 0;
             if (R[d].status) { d++; fresh = true; continue; }                    // a block CRC of an earlier slot batch has failed it
+            BatchSrc src = {cand, base[d] * 8, offh[d + 1] - offh[d], nullptr};
+            int term = 0;
             if (fresh) {
-                term = check_header(S, len >= 4, head[d], &dbufSize);            // :137-152, before anything else
-                p = 32; streamCRC = 0; fresh = false;
+                c = {32, 0, 0};
+                term = check_header(S, src.len >= 4, head[d], &c.dbufSize);      // :137-152, before anything else
+                fresh = false;
             }
-            while (!term) {
-                if (eof(p)) break;                                               // :462
-                const u64 key = (B + p) << 1;
-                auto it = std::lower_bound(cand.begin(), cand.end(), key, [](const DecCand& x, u64 k) { return x.key < k; });
-                if (it == cand.end() || (it->key >> 1) != B + p) { term = fail(S, DEC_NOT_BZIP, DEC_DETAIL_NONE); break; }     // :160-161
-                if (it->key & 1u) {                                              // end of stream :157-159,:465-477
-                    if (it->a != streamCRC) { term = fail(S, DEC_DATA_ERROR, DEC_DETAIL_STREAM_CRC, streamCRC, it->a); break; }
-                    if (multistream && !eof(p + 80)) {
-                        const u64 nb = (p + 80 + 7) >> 3;
-                        term = check_header(S, len >= nb + 4, it->b, &dbufSize);
-                        if (term) break;
-                        p = (nb + 4) * 8;
-                        streamCRC = 0;
-                        continue;
-                    }
-                    break;
-                }
-                const u32 idx = (u32)(std::lower_bound(bpos.begin(), bpos.end(), B + p) - bpos.begin());
-                if (idx < bfirst || idx >= bfirst + bcount) { need_batch = true; need = idx; break; }
-                const DecResult& r = res[idx - bfirst];
-                streamCRC = r.crc ^ ((streamCRC << 1) | (streamCRC >> 31));      // :163-164
-                term = block_error(S, r, dbufSize);
-                if (term) break;
-                valid.push_back({idx - bfirst, r.crc, d});
-                p = r.endbit - B;
-            }
-            if (need_batch) break;
-            if (term) doc_fail(S, R[d], term);           // (a block CRC found by process_valid_docs in front of it still wins)
+            if (!term) term = walk_chain(S, src, c, multistream, true, w, valid, &need);
+            vdoc.resize(valid.size(), d);
+            if (term > 0) break;                         // document d waits for the slot batch from `need` on
+            if (term) doc_fail(S, R[d], term);           // (a block CRC found by append_docs in front of it still wins)
             d++; fresh = true;
         }
-        rc = process_valid_docs(S, st, valid, R);
+        rc = append_docs(S, st, valid, vdoc, R);
         if (rc) return rc;
         if (d == count) break;
         if (R[d].status) continue;                       // the document waiting for blocks has failed meanwhile: no batch for it
-        bfirst = need;
-        bcount = (u32)std::min<size_t>(S.slots, bpos.size() - need);
-        rc = decode_batch(S, st, bpos.data() + bfirst, bcount, res, blim.data() + bfirst);
+        rc = decode_from(S, st, w, need);
         if (rc) return rc;
     }
     S.detail = 0; S.crc_got = S.crc_want = 0;            // (cjs_bz2_last_detail is the single call's; a batch reports per document)
