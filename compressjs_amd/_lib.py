@@ -24,7 +24,7 @@ SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_devic
            "cjs_dbg_k1_rounds", "cjs_dbg_k1_periodic_blocks", "cjs_dbg_rc_div", "cjs_dbg_multi_mallocs", "cjs_dbg_multi_fallbacks", "cjs_dbg_multi_replans",
            "cjs_bwtc_compress_batch_bound", "cjs_bwtc_compress_batch", "cjs_bwtc_compress_batch_device", "cjs_dbg_bwtc_batch_syncs", "cjs_dbg_rc_div_device",
            "cjs_bwtc_decompress_batch", "cjs_bwtc_decompress_batch_device", "cjs_dbg_bwtc_dec_batch_syncs", "cjs_dbg_bwtc_dec_batch_fallbacks",
-           "cjs_unbwt_linear_batch", "cjs_dbg_k6_groups"]
+           "cjs_unbwt_linear_batch", "cjs_dbg_k6_groups", "cjs_dbg_defsum_triples"]
 
 
 class CompressjsAmdError(RuntimeError):
@@ -179,6 +179,9 @@ def load(path: str | None = None):
     if hasattr(L, "cjs_dbg_k6_groups"):          # (as above)
         L.cjs_dbg_k6_groups.restype = C.c_int
         L.cjs_dbg_k6_groups.argtypes = []
+    if hasattr(L, "cjs_dbg_defsum_triples"):     # (as above)
+        L.cjs_dbg_defsum_triples.restype = C.c_int32
+        L.cjs_dbg_defsum_triples.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_int]
     L.cjs_bz2_last_decode_ms.restype = C.c_float
     L.cjs_bz2_last_decode_ms.argtypes = [vp]
     if path is None:

@@ -108,7 +108,8 @@ class Context:
 
     def bwtc_compress_many(self, docs, level: int = 9) -> list:
         """Many independent inputs in one call (cjs_bwtc_compress_batch): one BWTC stream per document, each equal to
-        bwtc_compress(doc, level).  Levels 6-9 run the range coder on the GPU too, one coder per document."""
+        bwtc_compress(doc, level).  At every level the model of every block (FenwickModel for 6-9, DefSumModel for 1-5) and the
+        range coder, one coder per document, run on the GPU too."""
         arrs = [np.ascontiguousarray(d, dtype=np.uint8).reshape(-1) for d in docs]
         if not arrs:
             return []

@@ -8,7 +8,9 @@ void bwtc_block(bwtc_coder* c, uint32_t length, uint32_t pidx, const uint32_t* u
 void bwtc_block_triples(bwtc_coder* c, uint32_t length, uint32_t pidx, const uint32_t* used8, const uint32_t* sylt,
                         const uint32_t* tot, uint32_t ntri);
 int64_t bwtc_end(bwtc_coder* c);
-uint64_t bwtc_end_n(bwtc_coder* c, bool* overflow);   // the length also when the stream did not fit
+// (tests) the triples DefSumModel (levels 1-5) hands to the range coder for one block: sylt[k] = sy_f | lt_f << 16, tot[k] = tot_f;
+// returns their number, 0xFFFFFFFF when they do not fit `cap`
+uint32_t bwtc_defsum_triples(const uint16_t* sym, uint32_t nsym, uint32_t alphabetSize, uint32_t* sylt, uint32_t* tot, uint32_t cap);
 
 // Decoder side (BWTC.decompressFile, lib/BWTC.js:141-233): serial range decoder + models on the host;
 // every block is handed to `on_block` as the BWT string (MTF and zero-run coding already undone)

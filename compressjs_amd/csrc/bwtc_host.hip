@@ -234,7 +234,7 @@ struct DefSum {
             }
         }
     }
-    void encode(RangeEnc& rc, uint32_t symbol) {                             // :98-115
+    template <class RC> void encode(RC& rc, uint32_t symbol) {               // :94-111 (RC: RangeEnc, or the tests' recorder)
         uint32_t lt_f = prob[symbol];
         uint32_t sy_f = prob[symbol + 1] - lt_f;
         if (sy_f) { rc.encodeShift(sy_f, lt_f, 8); upd(symbol); return; }
@@ -338,15 +338,21 @@ int64_t bwtc_end(bwtc_coder* c) {
     return n;
 }
 
-// bwtc_end for a caller that lays streams back to back (cjs_bwtc_compress_batch, levels 1-5): the stream's length also when it
-// did not fit its buffer (*overflow; nothing was written beyond the buffer)
-uint64_t bwtc_end_n(bwtc_coder* c, bool* overflow) {
-    c->rc.encodeFreq(1, 2, 3);
-    c->rc.finish();
-    const uint64_t n = c->out.n;
-    *overflow = c->out.overflow;
-    delete c;
-    return n;
+// (tests, cjs_dbg_defsum_triples) DefSum::encode over one block's symbols with a recorder in the range coder's place: what the
+// model hands to encodeShift / encodeFreq, in K10's layout; encodeShift(sy, lt, s) is encodeFreq(sy, lt, 1 << s)
+namespace {
+struct TripleRec {
+    uint32_t *sylt, *tot, cap, n;
+    void encodeFreq(uint32_t sy_f, uint32_t lt_f, uint32_t tot_f) { if (n < cap) { sylt[n] = sy_f | (lt_f << 16); tot[n] = tot_f; } n++; }
+    void encodeShift(uint32_t sy_f, uint32_t lt_f, int shift) { encodeFreq(sy_f, lt_f, 1u << shift); }
+};
+}  // namespace
+uint32_t bwtc_defsum_triples(const uint16_t* sym, uint32_t nsym, uint32_t alphabetSize, uint32_t* sylt, uint32_t* tot, uint32_t cap) {
+    static thread_local DefSum dm;
+    dm.init(alphabetSize + 1, false);
+    TripleRec rec = {sylt, tot, cap, 0};
+    for (uint32_t i = 0; i < nsym; i++) dm.encode(rec, sym[i]);
+    return rec.n <= cap ? rec.n : 0xFFFFFFFFu;
 }
 
 // ---------------------------------------------------------------------------------------------

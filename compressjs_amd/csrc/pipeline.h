@@ -112,6 +112,9 @@ int k6_unbwt_batch(const K6Blk* d_B, u32 nblk, u32 max_n, const u8* dT, u8* dU, 
 int k2_run(Pipe P, u32 max_n, hipStream_t stream);
 // BWTC levels 6..9: FenwickModel of every block on the GPU -> (sy_f | lt_f << 16, tot_f) per encodeFreq call, [nb][stride] each
 int k10_model_run(Pipe P, u32* sylt, u32* tot, u32* ntri, u32 ostride, u32 ocap, hipStream_t stream);
+// BWTC levels 1..5: DefSumModel of every block on the GPU (k13_defsum_model.hip), K10's inputs and K10's output layout; a symbol
+// gives one or two triples, so rows of 2 x stride always hold a block
+int k13_defsum_run(Pipe P, u32* sylt, u32* tot, u32* ntri, u32 ostride, u32 ocap, hipStream_t stream);
 // Batched BWTC (cjs_bwtc_compress_batch*, k11_bwtc_coder.hip): document d of the batch is input bytes [off[d], off[d+1]) and becomes a
 // BWTC stream of its own, coded by a range coder of its own on the device.
 struct K11State {      // RangeCoder (lib/RangeCoder.js:27-34) of one document between two launches, and its write cursor

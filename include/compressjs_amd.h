@@ -74,12 +74,11 @@ int cjs_bwtc_last_times(cjs_ctx* ctx, float* out5);
  * output did not fit the rows the block pipeline has for it (not seen; no bytes rather than wrong ones).  Every byte reported
  * has been written by the call.  The device form takes device pointers throughout; the host form uploads once and downloads once.
  * cjs_last_device_ms / cjs_last_block_count report the batch call.
- * Levels 6-9 (FenwickModel) are the fast path: the range coder runs on the GPU as well, one coder per document
- * (k11_bwtc_coder.hip: lib/RangeCoder.js:27-140, lib/BWTC.js:42-79,137-138, lib/NoModel.js, lib/LogDistanceModel.js), and the batch
- * does not touch the host between upload and download; the host waits for the device three times per call, whatever `count`
- * (cjs_dbg_bwtc_batch_syncs; the block sort's own small read-backs per sub-batch not counted).
- * Levels 1-5 (DefSumModel, lib/BWTC.js:107) are NOT the fast path: the block stages run batched on the GPU, the model and the
- * coder on the host, document after document; the device form stages through the host for them. */
+ * Every level runs on the GPU: the model of every block (FenwickModel for levels 6-9: k10_bwtc_model.hip; DefSumModel, lib/BWTC.js:107,
+ * for levels 1-5: k13_defsum_model.hip) and the range coder, one coder per document (k11_bwtc_coder.hip: lib/RangeCoder.js:27-140,
+ * lib/BWTC.js:42-79,137-138, lib/NoModel.js, lib/LogDistanceModel.js).  The batch does not touch the host between upload and
+ * download; the host waits for the device three times per call (the host form: four, with its download), whatever `count` and
+ * `level` (cjs_dbg_bwtc_batch_syncs; the block sort's own small read-backs per sub-batch not counted). */
 int64_t cjs_bwtc_compress_batch_bound(uint64_t total_len, uint32_t count);
 int64_t cjs_bwtc_compress_batch_device(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, int level,
                                        void* d_out, uint64_t out_cap, uint64_t* d_out_off);
@@ -88,6 +87,14 @@ int64_t cjs_bwtc_compress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t*
 int cjs_dbg_bwtc_batch_syncs(cjs_ctx* ctx);      /* host<->device synchronisations the last batch call on ctx made itself */
 /* (tests) floor(range / tot) as the device coder computes it (lib/RangeCoder.js:81): host pointers, n pairs, one tiny kernel */
 int cjs_dbg_rc_div_device(const uint32_t* range, const uint32_t* tot, uint32_t n, uint32_t* out);
+/* (tests) DefSumModel (lib/DefSumModel.js:39-111, BWTC levels 1-5) alone over nb rows of symbols: row b is sym[b * stride ..) with
+ * nsym[b] <= stride symbols in [0, alpha[b]] (RUNA = 0, RUNB = 1, MTF index + 1; the model's size is alpha[b] + 1, alpha[b] <= 256).
+ * Out, per row: ntri[b] triples, the arguments of the range coder's encodeFreq calls in order (encodeShift(sy, lt, 8) as
+ * tot = 256): sylt[b * ostride + k] = sy_f | lt_f << 16, tot[b * ostride + k] = tot_f; ntri[b] = 0xFFFFFFFF if they did not fit
+ * ostride (2 * nsym[b] always fit).  Host pointers.  on_host = 0: one launch of the device model (k13_defsum_model.hip);
+ * on_host = 1: the host model the single call cjs_bwtc_compress uses, with a recorder in the coder's place. */
+int32_t cjs_dbg_defsum_triples(const uint16_t* sym, const uint32_t* nsym, const uint32_t* alpha, uint32_t nb, uint32_t stride,
+                               uint32_t* sylt, uint32_t* tot, uint32_t* ntri, uint32_t ostride, int on_host);
 
 /* Sharded encoding for multi-GPU runs (blocks are independent once the RLE1 split is known):
  * cjs_bz2_plan   = the readBlock chain of lib/Bzip2.js:913-922 over the whole (device) input;

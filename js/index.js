@@ -179,7 +179,7 @@ BWTC.compressFile = function(inStream, outStream, props) {           // lib/BWTC
   return deliver(addon.bwtcCompress(bytes, level, known ? bytes.length : -1), outStream);   // lib/Util.js:119-124
 };
 // Not in the reference: many independent inputs in one call, one BWTC stream each - [BWTC.compressFile(x, null, level) for every x],
-// bit for bit, each with its size declared (cjs_bwtc_compress_batch; levels 6-9 run one range coder per input on the GPU).
+// bit for bit, each with its size declared (cjs_bwtc_compress_batch; at every level the model of every block and one range coder per input run on the GPU).
 BWTC.compressFiles = function(inputs, props) {
   var level = (typeof props === 'number' && props >= 1 && props <= 9) ? props : 9;   // lib/BWTC.js:16-19
   need();
