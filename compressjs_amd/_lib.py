@@ -23,7 +23,8 @@ SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_devic
            "cjs_dbg_bwt_batch_time", "cjs_dbg_block_stages", "cjs_dbg_k1_sparse_rounds",
            "cjs_dbg_k1_rounds", "cjs_dbg_k1_periodic_blocks", "cjs_dbg_rc_div", "cjs_dbg_multi_mallocs", "cjs_dbg_multi_fallbacks", "cjs_dbg_multi_replans",
            "cjs_bwtc_compress_batch_bound", "cjs_bwtc_compress_batch", "cjs_bwtc_compress_batch_device", "cjs_dbg_bwtc_batch_syncs", "cjs_dbg_rc_div_device",
-           "cjs_bwtc_decompress_batch", "cjs_bwtc_decompress_batch_device", "cjs_dbg_bwtc_dec_batch_syncs", "cjs_dbg_bwtc_dec_batch_fallbacks",
+           "cjs_bwtc_decompress_batch", "cjs_bwtc_decompress_batch_device", "cjs_bwtc_decompress_batch_ex", "cjs_bwtc_decompress_batch_device_ex",
+           "cjs_dbg_bwtc_dec_batch_syncs", "cjs_dbg_bwtc_dec_batch_fallbacks",
            "cjs_unbwt_linear_batch", "cjs_dbg_k6_groups", "cjs_dbg_defsum_triples"]
 
 
@@ -176,6 +177,11 @@ def load(path: str | None = None):
         L.cjs_dbg_bwtc_dec_batch_fallbacks.argtypes = [vp]
         L.cjs_unbwt_linear_batch.restype = C.c_int32
         L.cjs_unbwt_linear_batch.argtypes = [vp, vp, vp, C.c_uint32, vp]
+    if hasattr(L, "cjs_bwtc_decompress_batch_ex"):   # (as above)
+        L.cjs_bwtc_decompress_batch_ex.restype = C.c_int64
+        L.cjs_bwtc_decompress_batch_ex.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint32]
+        L.cjs_bwtc_decompress_batch_device_ex.restype = C.c_int64
+        L.cjs_bwtc_decompress_batch_device_ex.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint32]
     if hasattr(L, "cjs_dbg_k6_groups"):          # (as above)
         L.cjs_dbg_k6_groups.restype = C.c_int
         L.cjs_dbg_k6_groups.argtypes = []
@@ -187,6 +193,9 @@ def load(path: str | None = None):
     if path is None:
         _lib = L
     return L
+
+
+BWTC_DEC_DEFSUM_DEVICE = 1      # CJS_BWTC_DEC_DEFSUM_DEVICE (cjs_bwtc_decompress_batch_ex*): levels 1-5 decoded on the GPU
 
 
 # Bunzip's errors (lib/Bzip2.js:62-88): TypeError with .errorCode, message + optional detail

@@ -251,8 +251,8 @@ class Context:
         return b""
 
     def bwtc_decompress_many(self, streams, return_errors: bool = False) -> list:
-        """Many independent BWTC streams in one call (cjs_bwtc_decompress_batch): entry d is bwtc_decompress(streams[d]).  Levels 6-9
-        run one range decoder per document on the GPU.  A document that fails raises what bwtc_decompress raises for it, with
+        """Many independent BWTC streams in one call (cjs_bwtc_decompress_batch_ex): entry d is bwtc_decompress(streams[d]).  Every
+        level runs one range decoder per document on the GPU (levels 1-5 through CJS_BWTC_DEC_DEFSUM_DEVICE).  A document that fails raises what bwtc_decompress raises for it, with
         .index = d (the first failing one) - or, with return_errors, that exception takes its place in the list and the other
         documents are still delivered."""
         arrs = [_coerce_input(s).reshape(-1) for s in streams]
@@ -265,13 +265,13 @@ class Context:
         out_off = np.zeros(count + 1, dtype=np.uint64)
         status = np.zeros(count, dtype=np.int32)
         out = self._staging(1)
-        n = self.L.cjs_bwtc_decompress_batch(self.h, flat.ctypes.data, off.ctypes.data, count, out.ctypes.data, 0, out_off.ctypes.data,
-                                             status.ctypes.data, None)
+        n = self.L.cjs_bwtc_decompress_batch_ex(self.h, flat.ctypes.data, off.ctypes.data, count, out.ctypes.data, 0, out_off.ctypes.data,
+                                                status.ctypes.data, None, _lib.BWTC_DEC_DEFSUM_DEVICE)
         if n == -21:                                   # sizes now known: fetch the retained result
             n = int(self.L.cjs_bwtc_last_size(self.h))
             out = self._staging(max(n, 1))
             n = self.L.cjs_bwtc_fetch(self.h, out.ctypes.data, n)
-        _lib.check(n, "cjs_bwtc_decompress_batch")
+        _lib.check(n, "cjs_bwtc_decompress_batch_ex")
         res = []
         for k in range(count):
             if status[k]:
@@ -287,8 +287,8 @@ class Context:
         return res
 
     def bwtc_decompress_many_device(self, d_in, d_off, d_out, d_out_off, d_status, d_declared=None) -> int:
-        """The same with everything resident in HBM: d_in / d_out torch uint8 CUDA tensors, d_off / d_out_off 64-bit integer CUDA
-        tensors of count + 1 elements, d_status an int32 CUDA tensor of count elements (0, -30 or -31; a failed document contributes
+        """The same (cjs_bwtc_decompress_batch_device_ex) with everything resident in HBM: d_in / d_out torch uint8 CUDA tensors,
+        d_off / d_out_off 64-bit integer CUDA tensors of count + 1 elements, d_status an int32 CUDA tensor of count elements (0, -30 or -31; a failed document contributes
         no bytes), d_declared an optional int64 CUDA tensor of count elements (the size every header records, -1: unknown).
         Returns the total number of decoded bytes."""
         import torch
@@ -304,10 +304,10 @@ class Context:
                 raise ValueError("%s: on another device than d_in" % name)
         if count < 0 or d_out_off.numel() < count + 1 or d_status.numel() < count or (d_declared is not None and d_declared.numel() < count):
             raise ValueError("d_off / d_out_off: count + 1 elements, d_status / d_declared: count")
-        n = self.L.cjs_bwtc_decompress_batch_device(self.h, d_in.data_ptr(), d_off.data_ptr(), count, d_out.data_ptr(), d_out.numel(),
-                                                    d_out_off.data_ptr(), d_status.data_ptr(),
-                                                    d_declared.data_ptr() if d_declared is not None else None)
-        return _lib.check(n, "cjs_bwtc_decompress_batch_device")
+        n = self.L.cjs_bwtc_decompress_batch_device_ex(self.h, d_in.data_ptr(), d_off.data_ptr(), count, d_out.data_ptr(), d_out.numel(),
+                                                       d_out_off.data_ptr(), d_status.data_ptr(),
+                                                       d_declared.data_ptr() if d_declared is not None else None, _lib.BWTC_DEC_DEFSUM_DEVICE)
+        return _lib.check(n, "cjs_bwtc_decompress_batch_device_ex")
 
     def decompress_device(self, d_in, d_out, multistream: bool = False) -> int:
         """Stream and output are torch uint8 CUDA tensors; returns the decoded size."""
@@ -553,8 +553,8 @@ class BWTC:
 
     @staticmethod
     def decompressFiles(inputs, return_errors=False):
-        """Many independent BWTC streams in one call (the reference has no batched entry): [BWTC.decompressFile(x) for x in
-        inputs]; a document that fails raises its error with .index set, or takes its place in the list with return_errors."""
+        """Many independent BWTC streams of any level in one call (the reference has no batched entry; cjs_bwtc_decompress_batch_ex
+        with levels 1-5 on the GPU too): [BWTC.decompressFile(x) for x in inputs]; a document that fails raises its error with .index set, or takes its place in the list with return_errors."""
         return default_context().bwtc_decompress_many([_coerce_input(x) for x in inputs], return_errors)
 
 

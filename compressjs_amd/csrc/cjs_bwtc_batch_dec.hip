@@ -2,15 +2,17 @@
 // include/compressjs_amd.h).  The reference has no batched entry: result d is what BWTC.decompressFile (lib/BWTC.js:141-233) gives
 // for document d alone, i.e. cjs_bwtc_decompress on it.
 //
-// The fast path - FenwickModel streams (levels 6-9) with their size declared: between upload and download everything runs on the
-// device.  k12_plan reads the headers and cuts the scratch, k12_decode runs one range decoder per document (one wave each),
+// The fast path - FenwickModel streams (levels 6-9) with their size declared, and with CJS_BWTC_DEC_DEFSUM_DEVICE in the `flags` of
+// the _ex entries DefSumModel streams (levels 1-5) too: between upload and download everything runs on the device.  k12_plan reads
+// the headers, cuts the scratch and counts the documents of either model, k12_decode (levels 6-9) and k14_decode (levels 1-5), each
+// launched only if it has documents, run one range decoder per document (one wave each),
 // k6_unbwt_batch inverts the BWT of all their blocks, group after group, and writes every block to its final place.  The host
 // waits THREE times, whatever the number of documents (cjs_dbg_bwtc_dec_batch_syncs):
 //   1  the plan's totals: how much scratch and how many block rows the admitted documents need (what is allocated);
 //   2  the documents' statuses and block rows: who failed, who takes the host path, where every block goes (out_off is the
 //      exclusive scan of the decoded sizes, made on the host from this one read-back);
 //   3  the end: the documents are in place (device form) or on the host.
-// The host path - DefSumModel streams (levels 1-5), no size declared, more bytes or blocks than declared, a size beyond the scratch
+// The host path - DefSumModel streams (levels 1-5) without that flag, no size declared, more bytes or blocks than declared, a size beyond the scratch
 // budget (CJS_BWTC_DEC_BUDGET bytes, 512 MiB unless set): bwtc_decode_one, what the single call runs, document after document,
 // with its own waits.  The device form brings these documents to the host and their bytes back.
 #include "cjs_ctx.h"
@@ -71,7 +73,7 @@ int run_groups(const std::vector<K6Blk>& rows, const std::vector<size_t>& ends, 
 // d_in / d_off on the device.  h_in / h_off: the same on the host, or null (the device form: fetched when a document needs the host
 // path).  dev: out / out_off / status / declared are device pointers, else host pointers.
 int64_t dec_batch(cjs_ctx* c, const u8* d_in, const u64* d_off, const u8* h_in, const u64* h_off, u32 count, bool dev, u8* out, u64 out_cap,
-                  u64* out_off, int32_t* status, int64_t* declared) {
+                  u64* out_off, int32_t* status, int64_t* declared, u32 flags_in) {
     hipStream_t st = c->stream;
     c->bwtc_dec_batch_syncs = 0;
     c->bwtc_dec_batch_fallbacks = 0;
@@ -94,6 +96,7 @@ int64_t dec_batch(cjs_ctx* c, const u8* d_in, const u64* d_off, const u8* h_in, 
     K12Plan Q;
     memset(&Q, 0, sizeof Q);
     Q.in = d_in; Q.off = d_off; Q.count = count; Q.budget = dec_budget();
+    Q.opt = (flags_in & CJS_BWTC_DEC_DEFSUM_DEVICE) ? K12_OPT_DEFSUM : 0u;
     Q.doc = (K12Doc*)c->bd[0];
     Q.flags = (u64*)((char*)c->bd[0] + doc_bytes);
     rc = k12_plan_run(Q, st);
@@ -110,8 +113,9 @@ int64_t dec_batch(cjs_ctx* c, const u8* d_in, const u64* d_off, const u8* h_in, 
     if (rc) return rc;
     Q.row = (K12Row*)c->bd[1];
     Q.scr = (u8*)c->bd[2];
-    // ---- one range decoder per document
-    rc = k12_decode_run(Q, st);
+    // ---- one range decoder per document: the kernel of either model, if the plan admitted documents of it
+    if (flags[K12_F_NFEN]) rc = k12_decode_run(Q, st);
+    if (!rc && flags[K12_F_NDEF]) rc = k14_decode_run(Q, st);
     if (rc) return rc;
     hrow.resize(nrows);
     HIP_CHECK_RET(hipMemcpyAsync(hdoc.data(), Q.doc, (size_t)count * sizeof(K12Doc), hipMemcpyDeviceToHost, st));
@@ -211,18 +215,18 @@ int64_t dec_batch(cjs_ctx* c, const u8* d_in, const u64* d_off, const u8* h_in, 
 
 }  // namespace
 
-extern "C" int64_t cjs_bwtc_decompress_batch_device(cjs_ctx* c, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,
-                                                    uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared) {
-    if (!c) return CJS_E_ARG;
+extern "C" int64_t cjs_bwtc_decompress_batch_device_ex(cjs_ctx* c, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,
+                                                       uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared, uint32_t flags) {
+    if (!c || (flags & ~CJS_BWTC_DEC_DEFSUM_DEVICE)) return CJS_E_ARG;
     if (count == 0) return 0;
     if (!d_off || !d_out_off || !d_status) return CJS_E_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return CJS_E_NOGPU;
-    return dec_batch(c, (const u8*)d_in, (const u64*)d_off, nullptr, nullptr, count, true, (u8*)d_out, out_cap, (u64*)d_out_off, d_status, d_declared);
+    return dec_batch(c, (const u8*)d_in, (const u64*)d_off, nullptr, nullptr, count, true, (u8*)d_out, out_cap, (u64*)d_out_off, d_status, d_declared, flags);
 }
 
-extern "C" int64_t cjs_bwtc_decompress_batch(cjs_ctx* c, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
-                                             uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared) {
-    if (!c) return CJS_E_ARG;
+extern "C" int64_t cjs_bwtc_decompress_batch_ex(cjs_ctx* c, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
+                                                uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared, uint32_t flags) {
+    if (!c || (flags & ~CJS_BWTC_DEC_DEFSUM_DEVICE)) return CJS_E_ARG;
     if (count == 0) return 0;
     if (!off || !out_off || !status) return CJS_E_ARG;
     for (u32 d = 0; d < count; d++) if (off[d + 1] < off[d]) return CJS_E_ARG;
@@ -238,9 +242,19 @@ extern "C" int64_t cjs_bwtc_decompress_batch(cjs_ctx* c, const uint8_t* in, cons
     u64* d_off = (u64*)((char*)c->din + off_at);
     if (total) HIP_CHECK_RET(hipMemcpyAsync(c->din, in + base, total, hipMemcpyHostToDevice, c->stream));
     HIP_CHECK_RET(hipMemcpyAsync(d_off, rel.data(), off_bytes, hipMemcpyHostToDevice, c->stream));
-    const int64_t n = dec_batch(c, (const u8*)c->din, d_off, in ? in + base : nullptr, rel.data(), count, false, out, out_cap, (u64*)out_off, status, declared);
+    const int64_t n = dec_batch(c, (const u8*)c->din, d_off, in ? in + base : nullptr, rel.data(), count, false, out, out_cap, (u64*)out_off, status, declared, flags);
     (void)hipStreamSynchronize(c->stream);                        // (`rel` is on its way up until the call's first wait; error paths included)
     return n;
+}
+
+// the entries without a flags word: flags = 0, levels 1-5 on the host path
+extern "C" int64_t cjs_bwtc_decompress_batch_device(cjs_ctx* c, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,
+                                                    uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared) {
+    return cjs_bwtc_decompress_batch_device_ex(c, d_in, d_off, count, d_out, out_cap, d_out_off, d_status, d_declared, 0u);
+}
+extern "C" int64_t cjs_bwtc_decompress_batch(cjs_ctx* c, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
+                                             uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared) {
+    return cjs_bwtc_decompress_batch_ex(c, in, off, count, out, out_cap, out_off, status, declared, 0u);
 }
 
 // BWT.unbwtransform (lib/BWT.js:352-363) of `count` blocks in one call: block k = T[off[k] .. off[k+1]) with primary index

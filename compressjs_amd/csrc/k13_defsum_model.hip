@@ -21,7 +21,8 @@
 //   triggers the rebuild: both triples of an escaped symbol come from the same tables.
 // Lane i writes its one or two triples at nout + i + E_(i-1); the update counts are LDS atomics (a symbol can repeat in a
 // chunk).  The rebuild (:54-80) runs wave-wide over the numSyms + 1 <= 258 entries, 64 at a time: newProb = (p >> 1) + update,
-// the cumulative probability from a DPP scan, the cumulative escape index and the odd count from ballots.
+// the cumulative probability from a DPP scan, the cumulative escape index and the odd count from ballots (k13_rebuild.h, which the
+// decoder K14 calls too).
 //
 // Row capacity: a symbol gives at most two triples, so a block gives at most 2 * nsym, and nsym = pos - 1 <= stride.  The batch
 // hands K13 the rows it hands K10, ostride = ocap = 2 * stride u32, which therefore always suffice; the check in front of every
@@ -31,12 +32,11 @@
 // No per-lane arrays (no scratch memory); prob, escape and update sit in LDS (3 x 264 u32).
 #include "pipeline.h"
 #include "bwtc_host.h"
+#include "k13_rebuild.h"
 #include <string.h>
 #include <vector>
 
 #define K10_OVERFLOW 0xFFFFFFFFu
-#define K13_TAB 264u                   // >= numSyms + 2 = alphabetSize + 3 <= 259
-#define K13_MAX_ESC 40u                // MAX_ESCAPE_COUNT  lib/DefSumModel.js:9
 
 __global__ __launch_bounds__(64) void k13_defsum(const u16* A, u32 stride, const u32* pos, const u32* alpha, u32* sylt, u32* tot,
                                                  u32* ntri, u32 ostride, u32 ocap) {
@@ -102,25 +102,8 @@ __global__ __launch_bounds__(64) void k13_defsum(const u16* A, u32 stride, const
         if (tl < th) { uc = tl; uesc += gl; continue; }       // :51 defer
         // the rebuild :54-80; the escape that met updateCount == updateThresh - 1 was refused  :46
         uesc += gl - (tl > th ? 1u : 0u);
-        __builtin_amdgcn_wave_barrier();
-        u32 cum = 0u, cume = 0u, odd = 0u;
-        for (u32 r = 0; r * 64u <= size; r++) {
-            const u32 i = r * 64u + lane;
-            const bool v = i <= size;
-            const u32 ii = v ? i : 0u;
-            const u32 np = v ? ((prob[ii + 1u] - prob[ii]) >> 1) + (i == size ? uesc : upd[ii]) : 0u;
-            const u32 inc = wave_incl_scan_dpp(np);
-            const u64 dead = __ballot(v && np == 0u);
-            const u64 oddm = __ballot((np & 1u) != 0u);
-            if (v) { prob[i] = cum + inc - np; esc[i] = cume + (u32)__popcll(dead & lt_lanes); upd[i] = 0u; }
-            cum += (u32)__builtin_amdgcn_readlane((int)inc, 63);
-            cume += (u32)__popcll(dead);
-            odd += (u32)__popcll(oddm);
-        }
-        if (lane == 0) prob[size + 1u] = cum;                 // :71 (= 256)
-        th = 256u - (cum - odd) / 2u;                         // :74
+        th = k13_rebuild(prob, esc, upd, size, uesc, lane, lt_lanes);
         uesc = 1u; uc = 1u;                                   // :79-80
-        __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) ntri[b] = nout;
 }

@@ -155,14 +155,17 @@ int k11_plan_run(K11Plan Q, hipStream_t stream);                                
 int k11_gather_run(K11Plan Q, Pipe P, u32 first, hipStream_t stream);                 // rows of P.T and P.nlen for blocks [first, first + P.g.nb)
 int k11_code_run(K11Plan Q, K11Sub S, hipStream_t stream);
 int k11_finish_run(K11Plan Q, u8* d_out, u64 out_cap, u64* d_out_off, u32 split, hipStream_t stream);   // out_off, then the streams to their places
-// Batched BWTC decode (cjs_bwtc_decompress_batch*, k12_bwtc_decoder.hip): document d is a BWTC stream of its own, decoded by a
+// Batched BWTC decode (cjs_bwtc_decompress_batch*, k12_bwtc_decoder.hip, k14_defsum_decoder.hip): document d is a BWTC stream of its own, decoded by a
 // range decoder of its own on the device, ONE WAVE per document.
 #define K12_HOST 1           // K12Doc.status: not the fast path - the host decodes this document (cjs_bwtc_decompress's machinery)
 #define K12_F_SCR 0          // flags[] (u64): bytes of scratch the admitted documents need
 #define K12_F_BLK 1          //                their block rows
 #define K12_F_BAD 2          //                the offsets decrease somewhere, or `in` is null with bytes to read
 #define K12_F_TOTAL 3        //                off[count]
-#define K12_F_WORDS 4
+#define K12_F_NFEN 4         //                admitted documents of levels 6-9 (FenwickModel: k12_decode)
+#define K12_F_NDEF 5         //                admitted documents of levels 1-5 (DefSumModel: k14_decode)
+#define K12_F_WORDS 6
+#define K12_OPT_DEFSUM 1u    // K12Plan.opt (= CJS_BWTC_DEC_DEFSUM_DEVICE): DefSumModel streams with a declared size are admitted
 struct K12Doc {
     u64 scrAt;         // the document's bytes in the scratch (dword aligned)
     long long declared;   // the size its header records (-1: none, or the header was not read that far)
@@ -175,6 +178,7 @@ struct K12Doc {
 struct K12Row { u32 len, pidx, place, pad; };   // one block: its MTF-decoded last column lies at scrAt + place
 struct K12Plan {
     const u8* in; const u64* off; u32 count;
+    u32 opt;           // K12_OPT_*
     u64 budget;        // bytes of scratch a call may take
     K12Doc* doc;       // [count]
     K12Row* row;       // [flags[K12_F_BLK]]
@@ -182,7 +186,8 @@ struct K12Plan {
     u64* flags;        // [K12_F_WORDS]
 };
 int k12_plan_run(K12Plan Q, hipStream_t stream);
-int k12_decode_run(K12Plan Q, hipStream_t stream);
+int k12_decode_run(K12Plan Q, hipStream_t stream);     // levels 6-9; the documents of the other model are left alone
+int k14_decode_run(K12Plan Q, hipStream_t stream);     // levels 1-5 (k14_defsum_decoder.hip)
 int k34_run(Pipe P, hipStream_t stream);
 int k3_alloc_lengths_run(long long* d_arr, const u32* d_off, u32 count, int maxlen, hipStream_t stream);
 // Batched compression (cjs_bz2_compress_batch*): document d of the batch is input bytes [off[d], off[d+1]) and becomes a .bz2 stream of

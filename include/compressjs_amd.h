@@ -302,7 +302,17 @@ int64_t cjs_bwtc_fetch(cjs_ctx* ctx, uint8_t* out, uint64_t out_cap);
  * The host path - DefSumModel streams (levels 1-5), no size declared, a document that holds more bytes or blocks than its header
  * declares, a declared size beyond what is left of the call's scratch budget (512 MiB; the memory a call takes is bounded by it,
  * never by what a header claims): decoded by the single call's machinery, document after document, same result, no speed claim
- * (cjs_dbg_bwtc_dec_batch_fallbacks counts them; they add their own waits).  The device form stages these through the host. */
+ * (cjs_dbg_bwtc_dec_batch_fallbacks counts them; they add their own waits).  The device form stages these through the host.
+ * The _ex forms take a `flags` word; flags = 0 is the call above, bit for bit, and an unknown bit is CJS_E_ARG.  With
+ * CJS_BWTC_DEC_DEFSUM_DEVICE a DefSumModel stream (levels 1-5) that declares its size takes the fast path too: its range decoder
+ * runs on the GPU, one wave per document (k14_defsum_decoder.hip: lib/DefSumModel.js:11-131 on K12's decoder), between the same
+ * three waits.  Every other reason for the host path stays, the contract is the same: result d is cjs_bwtc_decompress's for stream
+ * d alone, and the two counters report the _ex calls the same way. */
+#define CJS_BWTC_DEC_DEFSUM_DEVICE 1u   /* DefSumModel streams (levels 1-5) with a declared size: decoded on the GPU */
+int64_t cjs_bwtc_decompress_batch_ex(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
+                                     uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared, uint32_t flags);
+int64_t cjs_bwtc_decompress_batch_device_ex(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,
+                                            uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, int64_t* d_declared, uint32_t flags);
 int64_t cjs_bwtc_decompress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t* off, uint32_t count, uint8_t* out,
                                   uint64_t out_cap, uint64_t* out_off, int32_t* status, int64_t* declared);
 int64_t cjs_bwtc_decompress_batch_device(cjs_ctx* ctx, const void* d_in, const uint64_t* d_off, uint32_t count, void* d_out,

@@ -19,6 +19,7 @@
 #include <sys/mman.h>
 
 typedef struct cjs_ctx cjs_ctx;
+static const uint32_t BWTC_DEC_DEFSUM_DEVICE = 1u;      // CJS_BWTC_DEC_DEFSUM_DEVICE of include/compressjs_amd.h
 static cjs_ctx* (*p_create)(int, uint32_t);
 static void (*p_destroy)(cjs_ctx*);
 static int64_t (*p_bound)(uint64_t);
@@ -45,7 +46,7 @@ static int64_t (*p_bwtc_dec)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint6
 static int64_t (*p_bwtc_lastsize)(cjs_ctx*);
 static int64_t (*p_bwtc_fetch)(cjs_ctx*, uint8_t*, uint64_t);
 static int64_t (*p_bwtc_bound)(uint64_t);
-static int64_t (*p_bwtc_dec_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*);
+static int64_t (*p_bwtc_dec_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*, uint32_t);   // the _ex entry
 static int64_t (*p_bwtc)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t);
 static void* g_lib;
 static cjs_ctx* g_ctx;                       // context on the first configured device: every single-device entry point
@@ -84,7 +85,7 @@ static bool load_lib(const char* path) {
     p_bwtc_lastsize = (int64_t(*)(cjs_ctx*))dlsym(g_lib, "cjs_bwtc_last_size");
     p_bwtc_fetch = (int64_t(*)(cjs_ctx*, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bwtc_fetch");
     p_bwtc_bound = (int64_t(*)(uint64_t))dlsym(g_lib, "cjs_bwtc_compress_bound");
-    p_bwtc_dec_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*))dlsym(g_lib, "cjs_bwtc_decompress_batch");
+    p_bwtc_dec_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, int64_t*, uint32_t))dlsym(g_lib, "cjs_bwtc_decompress_batch_ex");
     p_bwtc = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint8_t*, uint64_t, int64_t))dlsym(g_lib, "cjs_bwtc_compress");
     p_bwtc_batch_bound = (int64_t(*)(uint64_t, uint32_t))dlsym(g_lib, "cjs_bwtc_compress_batch_bound");
     p_bwtc_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*))dlsym(g_lib, "cjs_bwtc_compress_batch");
@@ -617,7 +618,8 @@ static napi_value BwtcDecompress(napi_env env, napi_callback_info info) {
 }
 
 // bwtcDecompressMany(buffers, returnErrors) -> [Buffer | Error]   = [BWTC.decompressFile(x) for every x] in one call
-// (cjs_bwtc_decompress_batch; levels 6-9 run one range decoder per input on the GPU).  A document that fails throws what
+// (cjs_bwtc_decompress_batch_ex with CJS_BWTC_DEC_DEFSUM_DEVICE: every level runs one range decoder per input on the GPU).  A
+// document that fails throws what
 // bwtcDecompress throws for it, with .index - or, with returnErrors, that error object takes its place in the array.
 static napi_value BwtcDecompressMany(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value argv[2];
@@ -643,14 +645,14 @@ static napi_value BwtcDecompressMany(napi_env env, napi_callback_info info) {
     std::vector<uint8_t> flat((size_t)(total ? total : 1));
     for (uint32_t i = 0; i < count; i++) if (off[i + 1] > off[i]) memcpy(flat.data() + off[i], ptr[i], (size_t)(off[i + 1] - off[i]));
     std::vector<int32_t> status(count, 0);
-    int64_t n = p_bwtc_dec_batch(g_ctx, flat.data(), off.data(), count, nullptr, 0, out_off.data(), status.data(), nullptr);
+    int64_t n = p_bwtc_dec_batch(g_ctx, flat.data(), off.data(), count, nullptr, 0, out_off.data(), status.data(), nullptr, BWTC_DEC_DEFSUM_DEVICE);
     std::vector<uint8_t> outb;
     if (n == -21) {                                            // decoded; the sizes are known now
         n = p_bwtc_lastsize(g_ctx);
         outb.resize((size_t)(n > 0 ? n : 1));
         n = p_bwtc_fetch(g_ctx, outb.data(), (uint64_t)n);
     }
-    if (n < 0) return throw_code(env, n, "cjs_bwtc_decompress_batch");
+    if (n < 0) return throw_code(env, n, "cjs_bwtc_decompress_batch_ex");
     for (uint32_t i = 0; i < count; i++) {
         napi_value b; void* dst;
         if (status[i]) {

@@ -192,8 +192,8 @@ BWTC.decompressFile = function(inStream, outStream) {               // lib/BWTC.
   var bytes = inputBytes(inStream);
   return deliver(addon.bwtcDecompress(bytes), outStream);
 };
-// Not in the reference: many independent BWTC streams in one call - [BWTC.decompressFile(x) for every x] (cjs_bwtc_decompress_batch;
-// levels 6-9 run one range decoder per input on the GPU).  An input that fails throws what decompressFile throws for it, with
+// Not in the reference: many independent BWTC streams in one call - [BWTC.decompressFile(x) for every x] (cjs_bwtc_decompress_batch_ex;
+// every level, 1-5 included, runs one range decoder per input on the GPU).  An input that fails throws what decompressFile throws for it, with
 // .index - or, with returnErrors, that error takes its place in the array and the others are still delivered.
 BWTC.decompressFiles = function(inputs, returnErrors) {
   need();
