@@ -25,7 +25,8 @@ SYMBOLS = ["cjs_create", "cjs_destroy", "cjs_device_count", "cjs_lcg_ascii_devic
            "cjs_bwtc_compress_batch_bound", "cjs_bwtc_compress_batch", "cjs_bwtc_compress_batch_device", "cjs_dbg_bwtc_batch_syncs", "cjs_dbg_rc_div_device",
            "cjs_bwtc_decompress_batch", "cjs_bwtc_decompress_batch_device", "cjs_bwtc_decompress_batch_ex", "cjs_bwtc_decompress_batch_device_ex",
            "cjs_dbg_bwtc_dec_batch_syncs", "cjs_dbg_bwtc_dec_batch_fallbacks",
-           "cjs_unbwt_linear_batch", "cjs_dbg_k6_groups", "cjs_dbg_defsum_triples"]
+           "cjs_unbwt_linear_batch", "cjs_dbg_k6_groups", "cjs_dbg_defsum_triples",
+           "cjs_bz2_decompress_blocks", "cjs_bz2_decompress_blocks_device"]
 
 
 class CompressjsAmdError(RuntimeError):
@@ -146,6 +147,11 @@ def load(path: str | None = None):
         L.cjs_bz2_decompress_batch_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp, vp]
         L.cjs_dbg_dec_syncs.restype = C.c_int
         L.cjs_dbg_dec_syncs.argtypes = []
+    if hasattr(L, "cjs_bz2_decompress_blocks"):  # (as above: absent from an older library loaded for A/B timing)
+        L.cjs_bz2_decompress_blocks.restype = C.c_int64
+        L.cjs_bz2_decompress_blocks.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+        L.cjs_bz2_decompress_blocks_device.restype = C.c_int64
+        L.cjs_bz2_decompress_blocks_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
     L.cjs_bz2_decompress_block.restype = C.c_int64
     L.cjs_bz2_decompress_block.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     L.cjs_bz2_table.restype = C.c_int64

@@ -226,6 +226,63 @@ class Context:
             _lib.raise_decode_error(self.L, self.h, int(n))
         return b""
 
+    def decompress_blocks(self, stream, positions, return_errors: bool = False) -> list:
+        """Many blocks of one stream in one call (cjs_bz2_decompress_blocks): index once with table, fetch many.  Entry k is
+        decompress_block(stream, positions[k]); positions are bit positions below 2**64, in any order, duplicates allowed.  A
+        request that fails raises what decompress_block would raise for it, with .index = k (the first failing one) - or, with
+        return_errors, that exception instance takes its place in the list and the other blocks are still delivered."""
+        d = _coerce_input(stream).reshape(-1)
+        pos = np.array([int(p) for p in positions], dtype=np.uint64)
+        count = int(pos.size)
+        if not count:
+            return []
+        out_off = np.zeros(count + 1, dtype=np.uint64)
+        status = np.zeros(count, dtype=np.int32)
+        detail = np.zeros(3 * count, dtype=np.uint32)
+        out = self._staging(1)
+        n = self.L.cjs_bz2_decompress_blocks(self.h, d.ctypes.data if d.size else None, d.size, pos.ctypes.data, count,
+                                             out.ctypes.data, 0, out_off.ctypes.data, status.ctypes.data, detail.ctypes.data)
+        if n == -21:                                   # sizes now known: fetch the retained result
+            n = int(self.L.cjs_bz2_last_size(self.h))
+            out = self._staging(max(n, 1))
+            n = self.L.cjs_bz2_fetch(self.h, out.ctypes.data, n)
+        _lib.check(n, "cjs_bz2_decompress_blocks")
+        res = []
+        for k in range(count):
+            if status[k]:
+                err = _lib.decode_error(int(status[k]), int(detail[3 * k]), int(detail[3 * k + 1]), int(detail[3 * k + 2]))
+                err.index = k
+                if not return_errors:
+                    raise err
+                res.append(err)
+            else:
+                res.append(out[int(out_off[k]):int(out_off[k + 1])].tobytes())
+        return res
+
+    def decompress_blocks_device(self, d_in, d_pos, d_out, d_out_off, d_status, d_detail=None) -> int:
+        """The same with everything resident in HBM: d_in (the stream) / d_out torch uint8 CUDA tensors, d_pos a 64-bit integer CUDA
+        tensor of count bit positions, d_out_off one of count + 1 elements, d_status an int32 CUDA tensor of count elements (0 or
+        the reference's Err code of request k; a failed request contributes no bytes), d_detail an optional 32-bit CUDA tensor of
+        3 * count elements.  Returns the total number of decoded bytes."""
+        import torch
+        count = int(d_pos.numel())
+        i64 = (torch.int64, getattr(torch, "uint64", torch.int64))
+        i32 = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for name, t, dt in (("d_in", d_in, (torch.uint8,)), ("d_out", d_out, (torch.uint8,)), ("d_pos", d_pos, i64),
+                            ("d_out_off", d_out_off, i64), ("d_status", d_status, (torch.int32,)), ("d_detail", d_detail, i32)):
+            if t is None and name == "d_detail":
+                continue
+            if t.dtype not in dt or not t.is_contiguous():
+                raise ValueError("%s: a contiguous tensor of dtype %s" % (name, dt[0]))
+            if t.device != d_in.device:
+                raise ValueError("%s: on another device than d_in" % name)
+        if d_out_off.numel() < count + 1 or d_status.numel() < count or (d_detail is not None and d_detail.numel() < 3 * count):
+            raise ValueError("d_out_off: count + 1 elements, d_status: count, d_detail: 3 * count")
+        n = self.L.cjs_bz2_decompress_blocks_device(self.h, d_in.data_ptr(), d_in.numel(), d_pos.data_ptr(), count,
+                                                    d_out.data_ptr(), d_out.numel(), d_out_off.data_ptr(), d_status.data_ptr(),
+                                                    d_detail.data_ptr() if d_detail is not None else None)
+        return _lib.check(n, "cjs_bz2_decompress_blocks_device")
+
     def table(self, stream, multistream: bool = False):
         """Bzip2.table (lib/Bzip2.js:508-548) -> [(bit position, decoded bytes)]."""
         d = np.ascontiguousarray(stream, dtype=np.uint8)
@@ -493,6 +550,12 @@ class Bzip2:
         """Bzip2.decompressBlock = Bunzip.decodeBlock (lib/Bzip2.js:482-503)."""
         data = _coerce_input(inStream)
         return _deliver(default_context().decompress_block(data, bitPos), outStream)
+
+    @staticmethod
+    def decompressBlocks(inStream, bitPositions, return_errors=False):
+        """Many blocks of one stream in one trip through the GPU (the reference has no batched entry): index once with table, then
+        [Bzip2.decompressBlock(inStream, p) for p in bitPositions]; a request that fails raises its error with .index set."""
+        return default_context().decompress_blocks(_coerce_input(inStream), bitPositions, return_errors)
 
     @staticmethod
     def table(inStream, callback, multistream=False):

@@ -500,3 +500,30 @@ extern "C" int64_t cjs_bz2_decompress_batch_device(cjs_ctx* c, const uint8_t* d_
                                                    uint32_t* d_detail) {
     return dec_batch_call(c, d_in, d_off, count, multistream, d_out, out_cap, d_out_off, d_status, d_detail, true);
 }
+
+// A list of blocks of one stream (declared in include/compressjs_amd.h): request k decodes as Bzip2.decompressBlock (lib/Bzip2.js:482-503)
+// does at bitpos[k] alone; the request level is in decode.hip (dec_blocks) and k7_blocks.hip.
+static int64_t dec_blocks_call(cjs_ctx* c, const uint8_t* in, uint64_t in_len, const uint64_t* bitpos, uint32_t count, uint8_t* out,
+                               uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail, bool dev) {
+    if (!c) return CJS_E_ARG;
+    if (count == 0) return 0;
+    if ((!in && in_len) || !bitpos || !out_off || !status) return CJS_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return CJS_E_NOGPU;
+    (void)hipEventRecord(c->ev0, c->stream);
+    const int64_t n = dec_blocks(&c->dec, dec_slots(c), c->stream, in, in_len, (const u64*)bitpos, count, dev, (u64*)out_off, status, detail);
+    (void)hipEventRecord(c->ev1, c->stream);
+    dec_sync_note();
+    (void)hipStreamSynchronize(c->stream);
+    c->dec_ms = 0.f;
+    (void)hipEventElapsedTime(&c->dec_ms, c->ev0, c->ev1);
+    return dec_deliver(c, n, out, out_cap, dev);
+}
+extern "C" int64_t cjs_bz2_decompress_blocks(cjs_ctx* c, const uint8_t* in, uint64_t in_len, const uint64_t* bitpos, uint32_t count,
+                                             uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail) {
+    return dec_blocks_call(c, in, in_len, bitpos, count, out, out_cap, out_off, status, detail, false);
+}
+extern "C" int64_t cjs_bz2_decompress_blocks_device(cjs_ctx* c, const uint8_t* d_in, uint64_t in_len, const uint64_t* d_bitpos, uint32_t count,
+                                                    uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status,
+                                                    uint32_t* d_detail) {
+    return dec_blocks_call(c, d_in, in_len, d_bitpos, count, d_out, out_cap, d_out_off, d_status, d_detail, true);
+}

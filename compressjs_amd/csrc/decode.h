@@ -83,6 +83,14 @@ int k7_scan_batch(const u8* d_st, u64 staged, const u64* d_off, const u64* d_bas
 int k9_docs_finish(const DecDocRec* d_rec, u32 count, u64* d_out_off, int* d_status, u32* d_detail, hipStream_t stream);
 int k9_docs_compact(const DecDocRec* d_rec, u32 count, const u8* d_src, u8* d_dst, u64 total, hipStream_t stream);
 
+// a list of block requests on one staged stream (k7_blocks.hip): the class of every request, the block requests compacted in request
+// order into d_cand (pos << 1) / d_reqOf, d_head[0] = their number, d_head[1] = the stream's 4-byte header.  d_wgTot: a u32 per 256 requests
+#define DEC_REQ_NEITHER 0u
+#define DEC_REQ_BLOCK 1u
+#define DEC_REQ_END 2u
+int k7_blocks(const u32* d_in32, u64 len, const u64* d_bitpos, u32 count, u8* d_cls, u32* d_wgTot, u64* d_cand, u32* d_reqOf,
+              u32* d_head, hipStream_t stream);
+
 int k7_scan(const u8* d_in, u64 len, u64 first_bit, u64* d_cand, u32* d_ncand, u32 cap, hipStream_t stream);
 int k7_run(DecBuf D, u32 first, u32 count, hipStream_t stream);
 int k8_run(DecBuf D, u32 nvalid, hipStream_t stream);

@@ -503,6 +503,48 @@ static int append_docs(DecState& S, hipStream_t st, std::vector<ValidBlk>& valid
     return 0;
 }
 
+// The outcome records of a call's documents (requests): failed ones contribute nothing and the gaps they left in the decoded bytes are
+// closed; out_off / status / detail go to the caller's arrays (dev: device pointers, through d_rec).  Returns the total.
+static int64_t docs_deliver(DecState& S, hipStream_t st, const std::vector<DocOut>& R, DecDocRec* d_rec, bool dev, u64* out_off,
+                            int* status, u32* detail) {
+    const u32 count = (u32)R.size();
+    int rc = 0;
+    // failed documents contribute nothing; the gaps they left are closed
+    std::vector<DecDocRec> rec((size_t)count + 1);
+    u64 total = 0;
+    bool gap = false;
+    for (u32 k = 0; k < count; k++) {
+        const DocOut& o = R[k];
+        const u64 n = o.status ? 0 : o.size;
+        if (n && o.src != total) gap = true;
+        rec[k] = {o.src, total, o.status, o.detail, o.got, o.want};
+        total += n;
+    }
+    rec[count] = {0, total, 0, 0, 0, 0};
+    if (dev || gap) TRYH(hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(DecDocRec), hipMemcpyHostToDevice, st));
+    if (gap) {
+        u8* q = nullptr;
+        TRYH(hipMalloc((void**)&q, S.out_cap));
+        rc = k9_docs_compact(d_rec, count, S.d_out, q, total, st);
+        const hipError_t e = dec_sync(st);
+        if (rc || e != hipSuccess) { (void)hipFree(q); return rc ? rc : CJS_E_HIP - (int)e; }
+        (void)hipFree(S.d_out);
+        S.d_out = q;
+    }
+    S.out_size = total;
+    if (dev) {
+        rc = k9_docs_finish(d_rec, count, out_off, status, detail, st);
+        if (rc) return rc;
+    } else {
+        for (u32 k = 0; k <= count; k++) out_off[k] = rec[k].dst;
+        for (u32 k = 0; k < count; k++) {
+            status[k] = rec[k].status;
+            if (detail) { detail[3 * (size_t)k] = rec[k].detail; detail[3 * (size_t)k + 1] = rec[k].got; detail[3 * (size_t)k + 2] = rec[k].want; }
+        }
+    }
+    return (int64_t)total;
+}
+
 int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const u64* off, u32 count, bool dev, int multistream,
                   u64* out_off, int* status, u32* detail) {
     int rc = dec_begin(ps, slots);
@@ -606,41 +648,91 @@ int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const 
         if (rc) return rc;
     }
     S.detail = 0; S.crc_got = S.crc_want = 0;            // (cjs_bz2_last_detail is the single call's; a batch reports per document)
+    return docs_deliver(S, st, R, d_rec, dev, out_off, status, detail);
+}
 
-    // results: failed documents contribute nothing; the gaps they left are closed
-    std::vector<DecDocRec> rec((size_t)count + 1);
-    u64 total = 0;
-    bool gap = false;
-    for (u32 k = 0; k < count; k++) {
-        const DocOut& o = R[k];
-        const u64 n = o.status ? 0 : o.size;
-        if (n && o.src != total) gap = true;
-        rec[k] = {o.src, total, o.status, o.detail, o.got, o.want};
-        total += n;
+// ---------------------------------------------------------------------------------------------
+// A list of blocks of one stream (cjs_bz2_decompress_blocks): request k decodes as Bunzip.decodeBlock (lib/Bzip2.js:482-503) does at
+// bitpos[k] alone.  The stream is staged once; k7_blocks.hip classifies the requests and compacts the block requests into the
+// candidate list on the device, so neither form reads 48 bits per request through the host; the block requests then go through
+// shared slot batches (k7_decode, the reference's block checks, K8/K9, CRC) and the outcome records of a batch of documents.
+// Waits: one for the probe, then one k7 and two K8/K9 waits per slot batch.
+// ---------------------------------------------------------------------------------------------
+int64_t dec_blocks(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 len, const u64* bitpos, u32 count, bool dev,
+                   u64* out_off, int* status, u32* detail) {
+    int rc = dec_begin(ps, slots);
+    if (rc) return rc;
+    DecState& S = **ps;
+    if (count > (1u << 27)) return CJS_E_UNSUPPORTED;                            // the cap on candidates
+    rc = stage_input(S, in, len, dev, st);                                       // (candLim = null: a single stream)
+    if (rc) return rc;
+    // device side: positions (host form) | classes | workgroup totals | candidates | request of candidate | head | outcome records
+    const size_t nwg = ((size_t)count + 255) / 256;
+    const size_t o_pos = 0, o_cls = al((size_t)count * 8), o_wg = o_cls + al(count), o_cand = o_wg + al(nwg * 4);
+    const size_t o_req = o_cand + al((size_t)count * 8), o_head = o_req + al((size_t)count * 4), o_rec = o_head + al(8);
+    rc = grow_dev(&S.d_meta, &S.meta_cap, o_rec + al(((size_t)count + 1) * sizeof(DecDocRec)));
+    if (rc) return rc;
+    u8* M = (u8*)S.d_meta;
+    const u64* d_pos = bitpos;
+    if (!dev) {
+        TRYH(hipMemcpyAsync(M + o_pos, bitpos, (size_t)count * 8, hipMemcpyHostToDevice, st));
+        d_pos = (const u64*)(M + o_pos);
     }
-    rec[count] = {0, total, 0, 0, 0, 0};
-    if (dev || gap) TRYH(hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(DecDocRec), hipMemcpyHostToDevice, st));
-    if (gap) {
-        u8* q = nullptr;
-        TRYH(hipMalloc((void**)&q, S.out_cap));
-        rc = k9_docs_compact(d_rec, count, S.d_out, q, total, st);
-        const hipError_t e = dec_sync(st);
-        if (rc || e != hipSuccess) { (void)hipFree(q); return rc ? rc : CJS_E_HIP - (int)e; }
-        (void)hipFree(S.d_out);
-        S.d_out = q;
-    }
-    S.out_size = total;
-    if (dev) {
-        rc = k9_docs_finish(d_rec, count, out_off, status, detail, st);
+    u64* d_cand = (u64*)(M + o_cand);
+    rc = k7_blocks(S.D.in32, len, d_pos, count, M + o_cls, (u32*)(M + o_wg), d_cand, (u32*)(M + o_req), (u32*)(M + o_head), st);
+    if (rc) return rc;
+    u32 head[2] = {0, 0};
+    std::vector<u8> cls(count);
+    std::vector<u32> reqOf(count);
+    TRYH(hipMemcpyAsync(head, M + o_head, 8, hipMemcpyDeviceToHost, st));
+    TRYH(hipMemcpyAsync(cls.data(), M + o_cls, count, hipMemcpyDeviceToHost, st));
+    TRYH(hipMemcpyAsync(reqOf.data(), M + o_req, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    TRYH(dec_sync(st));
+    const u32 nblk = std::min(head[0], count);
+
+    std::vector<DocOut> R(count, DocOut{0, 0, 0, 0, 0, 0, false});
+    u32 dbufSize = 0;
+    const int hrc = check_header(S, len >= 4, head[1], &dbufSize);               // :137-152 (new Bunzip), before anything else
+    if (hrc) for (DocOut& o : R) doc_fail(S, o, hrc);
+    else for (u32 k = 0; k < count; k++) if (cls[k] == DEC_REQ_NEITHER) doc_fail(S, R[k], fail(S, DEC_NOT_BZIP, DEC_DETAIL_NONE));   // :160-161
+    if (!hrc && nblk) {
+        rc = dec_fit_slots(S, slots, nblk);
         if (rc) return rc;
-    } else {
-        for (u32 k = 0; k <= count; k++) out_off[k] = rec[k].dst;
-        for (u32 k = 0; k < count; k++) {
-            status[k] = rec[k].status;
-            if (detail) { detail[3 * (size_t)k] = rec[k].detail; detail[3 * (size_t)k + 1] = rec[k].got; detail[3 * (size_t)k + 2] = rec[k].want; }
+        struct CandOf {                                  // k7_decode reads the compacted list; every other caller its own upload
+            DecState& S;
+            ~CandOf() { S.D.cand = S.d_bcand; }
+        } restore = {S};
+        S.D.cand = d_cand;
+        S.D.candLim = nullptr;
+        std::vector<DecResult> res;
+        std::vector<ValidBlk> valid;
+        std::vector<u32> size, crc;
+        std::vector<u64> outOff;
+        for (u32 first = 0; first < nblk; first += S.slots) {
+            const u32 n = std::min(S.slots, nblk - first);
+            rc = k7_run(S.D, first, n, st);
+            if (rc) return rc;
+            res.resize(n);
+            TRYH(hipMemcpyAsync(res.data(), S.D.res, (size_t)n * sizeof(DecResult), hipMemcpyDeviceToHost, st));
+            TRYH(dec_sync(st));
+            valid.clear();
+            for (u32 i = 0; i < n; i++) {
+                const int e = block_error(S, res[i], dbufSize);
+                if (e) doc_fail(S, R[reqOf[first + i]], e);
+                else valid.push_back({i, res[i].crc, 0});
+            }
+            rc = run_k8k9(S, st, valid, size, crc, outOff);
+            if (rc) return rc;
+            for (size_t v = 0; v < valid.size(); v++) {
+                DocOut& o = R[reqOf[first + valid[v].slot]];
+                o.src = outOff[v]; o.size = size[v];
+                S.out_size += size[v];
+                if (crc[v] != valid[v].crc) { o.status = DEC_DATA_ERROR; o.detail = DEC_DETAIL_BLOCK_CRC; o.got = crc[v]; o.want = valid[v].crc; }
+            }
         }
     }
-    return (int64_t)total;
+    S.detail = 0; S.crc_got = S.crc_want = 0;            // (cjs_bz2_last_detail is the single call's; a list reports per request)
+    return docs_deliver(S, st, R, (DecDocRec*)(M + o_rec), dev, out_off, status, detail);
 }
 
 const u8* dec_output(DecState* S, u64* size) { *size = S ? S->out_size : 0; return S ? S->d_out : nullptr; }

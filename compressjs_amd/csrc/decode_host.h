@@ -14,6 +14,11 @@ int64_t dec_block(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 le
 // failed documents contributing none) or a call-level error; per-document outcomes go to out_off / status / detail (may be null).
 int64_t dec_batch(DecState** ps, u32 slots, hipStream_t st, const u8* in, const u64* off, u32 count, bool dev, int multistream,
                   u64* out_off, int* status, u32* detail);
+// a list of blocks of one stream (cjs_bz2_decompress_blocks): request k decodes as dec_block does at bitpos[k] alone, without its
+// call-level errors: a bad stream header fails every request.  dev: in / bitpos / out_off / status / detail are device pointers.
+// Returns and delivers as dec_batch does, one record per request.
+int64_t dec_blocks(DecState** ps, u32 slots, hipStream_t st, const u8* in, u64 len, const u64* bitpos, u32 count, bool dev,
+                   u64* out_off, int* status, u32* detail);
 // host<->device synchronisations of the last decode call (dec_sync_note: one more, made by the caller on its behalf)
 int dec_sync_count();
 void dec_sync_note();

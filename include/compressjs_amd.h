@@ -266,6 +266,28 @@ int64_t cjs_bz2_decompress_batch(cjs_ctx* ctx, const uint8_t* in, const uint64_t
                                  uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail);
 int64_t cjs_bz2_decompress_batch_device(cjs_ctx* ctx, const uint8_t* d_in, const uint64_t* d_off, uint32_t count, int multistream,
                                         uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, uint32_t* d_detail);
+/* Batched block fetch: `count` chosen blocks of ONE stream in one call - index a .bz2 once with cjs_bz2_table, then fetch many blocks
+ * at random.  The reference has no batched entry; the contract is "equal to N single calls": result k is what
+ * Bzip2.decompressBlock(stream, bitpos[k]) = Bunzip.decodeBlock (lib/Bzip2.js:482-503) gives for that position ALONE.  The 4-byte
+ * stream header is checked first, as `new Bunzip` does (_start_bunzip, :137-152): a bad or missing one gives EVERY request status -2
+ * with detail 1 ('bad magic') or 2 ('level out of range') - not a call-level error.  Otherwise status[k] is 0 with the block's bytes
+ * where the 48 bits at bitpos[k] are the block magic, 0 with no bytes at the end-of-stream magic (_get_next_block, :157-159), -2 with
+ * detail 0 anywhere else (:160-161), the reference's block errors in its order (-7; -5 detail 3 'initial position out of bounds'
+ * :177-178; -5 detail 0), or -5 detail 4 on a block-CRC mismatch (:437-445) with CRC got / expected in detail[3k+1] / detail[3k+2]
+ * (`detail` may be NULL).  Positions are bit positions, in any order, duplicates allowed, any 64-bit value: bits behind the stream's end
+ * read as zeros (lib/BitStream.js:84), so a position at or behind 8 * in_len is -2.  Results lie back to back in request order: result
+ * k is out[out_off[k] .. out_off[k+1]), out_off has count + 1 entries, out_off[0] = 0; a failed request contributes no bytes and changes
+ * nothing for any other request.
+ * Both return the total number of decoded bytes (count == 0: 0).  Negative returns are call-level only: CJS_E_ARG (null ctx / bitpos /
+ * out_off / status, null `in` with in_len > 0), CJS_E_NOGPU, -100-hipError_t, CJS_E_UNSUPPORTED (more than 2^27 requests), and
+ * CJS_E_NOSPACE when out_cap is too small - out_off / status / detail have been written then and the bytes stay in HBM
+ * (cjs_bz2_last_size / cjs_bz2_fetch).  The device form takes device pointers throughout (d_bitpos included).  The stream is uploaded
+ * once and the requests are classified on the GPU; the number of host<->device waits does not depend on count while the block requests
+ * fit one slot batch.  cjs_bz2_last_decode_ms reports the call; cjs_bz2_last_detail reads 0 after it. */
+int64_t cjs_bz2_decompress_blocks(cjs_ctx* ctx, const uint8_t* in, uint64_t in_len, const uint64_t* bitpos, uint32_t count,
+                                  uint8_t* out, uint64_t out_cap, uint64_t* out_off, int32_t* status, uint32_t* detail);
+int64_t cjs_bz2_decompress_blocks_device(cjs_ctx* ctx, const uint8_t* d_in, uint64_t in_len, const uint64_t* d_bitpos, uint32_t count,
+                                         uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, int32_t* d_status, uint32_t* d_detail);
 int cjs_dbg_dec_syncs(void);          /* host<->device synchronisations (stream syncs, synchronous copies) of the last decode call of the process */
 
 /* = BWTC.decompressFile(input, output)   (reference: lib/BWTC.js:141-233 via Util.decompressFileHelper

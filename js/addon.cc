@@ -38,6 +38,7 @@ static int32_t (*p_hufflen)(int64_t*, uint32_t, uint32_t);
 static int64_t (*p_dec)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint64_t, int);
 static int64_t (*p_dec_batch)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*);
 static int64_t (*p_decblk)(cjs_ctx*, const uint8_t*, uint64_t, uint64_t, uint8_t*, uint64_t);
+static int64_t (*p_dec_blocks)(cjs_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*);
 static int64_t (*p_table)(cjs_ctx*, const uint8_t*, uint64_t, int, uint64_t*, uint64_t*, uint32_t);
 static int64_t (*p_lastsize)(cjs_ctx*);
 static int64_t (*p_fetch)(cjs_ctx*, uint8_t*, uint64_t);
@@ -77,6 +78,7 @@ static bool load_lib(const char* path) {
     p_dec = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, uint8_t*, uint64_t, int))dlsym(g_lib, "cjs_bz2_decompress");
     p_dec_batch = (int64_t(*)(cjs_ctx*, const uint8_t*, const uint64_t*, uint32_t, int, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*))dlsym(g_lib, "cjs_bz2_decompress_batch");
     p_decblk = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, uint64_t, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bz2_decompress_block");
+    p_dec_blocks = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, const uint64_t*, uint32_t, uint8_t*, uint64_t, uint64_t*, int32_t*, uint32_t*))dlsym(g_lib, "cjs_bz2_decompress_blocks");
     p_table = (int64_t(*)(cjs_ctx*, const uint8_t*, uint64_t, int, uint64_t*, uint64_t*, uint32_t))dlsym(g_lib, "cjs_bz2_table");
     p_lastsize = (int64_t(*)(cjs_ctx*))dlsym(g_lib, "cjs_bz2_last_size");
     p_fetch = (int64_t(*)(cjs_ctx*, uint8_t*, uint64_t))dlsym(g_lib, "cjs_bz2_fetch");
@@ -569,6 +571,62 @@ static napi_value DecompressMany(napi_env env, napi_callback_info info) {
     if (blk) stage_give(blk);
     return arr;
 }
+// decompressBlocks(bytes, bitPositions, returnErrors) -> [Buffer | TypeError]   = [Bzip2.decompressBlock(bytes, p) for every p] in one call
+// (cjs_bz2_decompress_blocks).  A position is a number or, above 2^53, a BigInt.  A request that fails throws what decompressBlock throws
+// for it, with .index - or, with returnErrors, that error object takes its place in the array.
+static napi_value DecompressBlocks(napi_env env, napi_callback_info info) {
+    size_t argc = 3; napi_value argv[3];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    uint8_t* in; size_t len; bool isarr = false, keep = false;
+    if (argc < 2 || !get_bytes(env, argv[0], &in, &len) || napi_is_array(env, argv[1], &isarr) != napi_ok || !isarr) {
+        napi_throw_type_error(env, nullptr, "decompressBlocks(bytes, bitPositions, returnErrors)"); return nullptr;
+    }
+    if (argc > 2) napi_get_value_bool(env, argv[2], &keep);
+    uint32_t count = 0;
+    napi_get_array_length(env, argv[1], &count);
+    std::vector<uint64_t> pos(count), out_off((size_t)count + 1, 0);
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value v; napi_valuetype t; double d = 0; bool lossless = false;
+        napi_get_element(env, argv[1], i, &v);
+        napi_typeof(env, v, &t);
+        if (t == napi_bigint && napi_get_value_bigint_uint64(env, v, &pos[i], &lossless) == napi_ok && lossless) continue;
+        if (t == napi_number && napi_get_value_double(env, v, &d) == napi_ok && d >= 0 && d < 18446744073709551616.0) { pos[i] = (uint64_t)d; continue; }
+        napi_throw_type_error(env, nullptr, "decompressBlocks(bytes, bitPositions, ...): every position must be a number or BigInt in [0, 2^64)");
+        return nullptr;
+    }
+    napi_value arr;
+    napi_create_array_with_length(env, count, &arr);
+    if (!count) return arr;
+    if (!ensure_ctx(env)) return nullptr;
+    if (!p_dec_blocks) return throw_code(env, -24, "cjs_bz2_decompress_blocks");
+    std::vector<int32_t> status(count, 0);
+    std::vector<uint32_t> detail((size_t)count * 3, 0);
+    int64_t n = p_dec_blocks(g_ctx, in, len, pos.data(), count, nullptr, 0, out_off.data(), status.data(), detail.data());
+    StageBlock* blk = nullptr;
+    if (n == -21) {                                            // decoded; the sizes are known now
+        n = p_lastsize(g_ctx);
+        blk = stage_take((uint64_t)n);
+        if (!blk) { napi_throw_error(env, nullptr, "out of memory"); return nullptr; }
+        n = p_fetch(g_ctx, blk->data, (uint64_t)n);
+        if (n >= 0 && (uint64_t)n > blk->hw) blk->hw = (uint64_t)n;
+    }
+    if (n < 0) { if (blk) stage_give(blk); return throw_code(env, n, "cjs_bz2_decompress_blocks"); }
+    for (uint32_t i = 0; i < count; i++) {
+        napi_value b; void* dst;
+        if (status[i]) {
+            b = decode_error(env, status[i], (int)detail[3 * (size_t)i], detail[3 * (size_t)i + 1], detail[3 * (size_t)i + 2]);
+            if (!b) { if (blk) stage_give(blk); return throw_code(env, status[i], "cjs_bz2_decompress_blocks"); }
+            napi_value idx;
+            napi_create_uint32(env, i, &idx);
+            napi_set_named_property(env, b, "index", idx);
+            if (!keep) { if (blk) stage_give(blk); napi_throw(env, b); return nullptr; }
+        } else if (out_off[i + 1] > out_off[i]) napi_create_buffer_copy(env, (size_t)(out_off[i + 1] - out_off[i]), blk->data + out_off[i], &dst, &b);
+        else napi_create_buffer(env, 0, &dst, &b);
+        napi_set_element(env, arr, i, b);
+    }
+    if (blk) stage_give(blk);
+    return arr;
+}
 // decompressBlock(bytes, bitPos) -> Buffer                        = Bzip2.decompressBlock
 static napi_value DecompressBlock(napi_env env, napi_callback_info info) {
     size_t argc = 2; napi_value argv[2];
@@ -701,6 +759,7 @@ static napi_value Init(napi_env env, napi_value exports) {
         {"unbwtransform", nullptr, UnBwtLinear, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decompress", nullptr, Decompress, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decompressMany", nullptr, DecompressMany, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"decompressBlocks", nullptr, DecompressBlocks, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"decompressBlock", nullptr, DecompressBlock, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"table", nullptr, Table, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"bwtcDecompress", nullptr, BwtcDecompress, nullptr, nullptr, nullptr, napi_default, nullptr},

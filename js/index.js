@@ -99,6 +99,15 @@ Bzip2.decompressBlock = function(input, bitPos, output) {            // lib/Bzip
   need();
   return deliver(addon.decompressBlock(inputBytes(input), bitPos), output);
 };
+// Not in the reference: many blocks of ONE stream in one call - index once with table, fetch many:
+// [decompressBlock(input, p) for every p of bitPositions] in one trip through the GPU (cjs_bz2_decompress_blocks; the stream is
+// uploaded once).  Positions are numbers or, above 2^53, BigInts; any order, duplicates allowed.  Returns an array of Buffers.  A
+// request that fails throws what decompressBlock throws for it (same constructor, errorCode and message) with .index set - or, with
+// returnErrors, that error takes its place in the array and the other blocks are still delivered.
+Bzip2.decompressBlocks = function(input, bitPositions, returnErrors) {
+  need();
+  return addon.decompressBlocks(inputBytes(input), Array.prototype.slice.call(bitPositions), !!returnErrors);
+};
 Bzip2.table = function(input, callback, multistream) {               // lib/Bzip2.js:508,933
   need();
   var t = addon.table(inputBytes(input), !!multistream);
